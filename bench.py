@@ -16,8 +16,16 @@ Inputs are resident in HBM before timing starts. value = payload GiB/s over all 
 = N * B * k * 1200 / 2^30 / step time (max over ranks). Multi-GPU: every rank owns its own
 2^20 contiguous blocks (weak scaling), no collective on the data path.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
+A plain run does what the headline figure needs and no more: it generates the batch, runs W
+warm-up steps, times K steps and prints the result line (metric, value, ms_per_step and the
+per-kernel event times of those same K steps). --dump-outputs DIR also writes what the last
+timed step computed (dump_outputs below). --full adds everything else the benchmark measures or
+checks, each in runs of its own after the timed steps: the full-batch round-trip check, the
+in-place reconstruct, the traffic twins and the roofline figures, the host-resident (PCIe)
+path, the oracle spot-check and the CPU baseline.
+
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts torchrun itself, as a
 child process, before anything touches the GPU, and exits with its status; it refuses (exit 2)
 when fewer than N devices are visible. Under torchrun, a WORLD_SIZE different from --gpus is
@@ -104,7 +112,12 @@ def parse():
     p.add_argument("--m", type=int, default=4)
     p.add_argument("--blocks", type=int, default=1 << 20, help="blocks per GPU")
     p.add_argument("--seed", type=int, default=0x0FEC)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the checks and the side measurements (round trip, "
+                        "in-place reconstruct, traffic twins / roofline, host-resident path, CPU baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step to DIR/<name>.npy (float32; see dump_outputs)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     p.add_argument("--cpu-sample-blocks", type=int, default=1 << 15)
     p.add_argument("--host-blocks", type=int, default=1 << 17,
                    help="blocks of the host-resident (PCIe-inclusive) measurement, rank 0 at N=1; 0: skip")
@@ -112,7 +125,40 @@ def parse():
                    help="diagnostics only: every torchrun rank on cuda:0 with gloo (RCCL refuses two ranks "
                         "on one device), to exercise the N>1 code path on a one-GPU box; its timings are "
                         "contended and never a result")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE_BLOCKS = 1024
+
+
+def dump_outputs(torch, batch, out_dir, seed):
+    """--dump-outputs: what the last timed step left in the buffers a caller of the hot path
+    receives, as float32 .npy files (byte values 0..255 and sums of them below 2^24, so exact):
+      parity.npy             [n, m, 1202]  parity shards (fec_rs_encode_batch) of n sampled blocks
+      recovered.npy          [n, 1202]     recovered shards (fec_rs_recover_batch) of the same blocks
+      sample_blocks.npy      [n]           the sampled block indices within this rank's batch (float64)
+      parity_block_sums.npy  [B]           sum of the m x 1202 parity bytes of every block
+      recovered_block_sums.npy [B]         sum of the 1202 recovered bytes of every block
+    n = min(B, 1024) blocks drawn once from numpy's default_rng(seed), ascending; the sums cover
+    the whole batch. About 33 MB at the default 2^20 blocks. Inputs come from the device generator
+    keyed by --seed, so two runs with the same arguments write the same files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    B = batch.B
+    pick = np.sort(np.random.default_rng(seed).choice(B, min(B, DUMP_SAMPLE_BLOCKS), replace=False))
+    idx = torch.from_numpy(pick).to(batch.parity.device)
+    arrays = {
+        "parity": batch.parity[idx][:, :, :SHARD_LEN].float(),
+        "recovered": batch.recovered[idx][:, 0, :SHARD_LEN].float(),
+        "sample_blocks": idx.double(),
+        "parity_block_sums": batch.parity[:, :, :SHARD_LEN].sum(dim=(1, 2), dtype=torch.int32).float(),
+        "recovered_block_sums": batch.recovered[:, 0, :SHARD_LEN].sum(dim=1, dtype=torch.int32).float(),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def padded(torch, shape, dev):
@@ -534,10 +580,13 @@ def main():
     batch = RankBatch(torch, codec, dev, B, k, m, args.seed, g_lo)
     step = RankStep(fec, codec, batch)
     encode, decode, decode_inplace = step.encode, step.decode, step.decode_inplace
-    encode()
-    decode()
-    codec.sync()
-    ok_roundtrip = step.check_full(torch)
+    full = args.full
+    ok_roundtrip = None
+    if full:
+        encode()
+        decode()
+        codec.sync()
+        ok_roundtrip = step.check_full(torch)
 
     for _ in range(args.warmup):
         encode()
@@ -564,15 +613,19 @@ def main():
     enc_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
     dec_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
     step_ms = wall * 1000.0 / args.steps
-    # in-place reconstruct, timed on its own (not part of the step)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = max(3, args.steps // 2)
-    e0.record(stream)
-    for _ in range(reps):
-        decode_inplace()
-    e1.record(stream)
-    codec.sync()
-    inplace_ms = e0.elapsed_time(e1) / reps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, batch, args.dump_outputs, args.seed)
+    inplace_ms = 0.0
+    if full:
+        # in-place reconstruct, timed on its own (not part of the step)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = max(3, args.steps // 2)
+        e0.record(stream)
+        for _ in range(reps):
+            decode_inplace()
+        e1.record(stream)
+        codec.sync()
+        inplace_ms = e0.elapsed_time(e1) / reps
     rank_step_ms = [step_ms]
     ranks_seen = 1
     if distributed:
@@ -584,9 +637,59 @@ def main():
         t = torch.tensor([step_ms, enc_ms, dec_ms, inplace_ms], device=rdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         step_ms, enc_ms, dec_ms, inplace_ms = t.tolist()
-        okt = torch.tensor([1 if ok_roundtrip else 0], device=rdev)
-        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-        ok_roundtrip = bool(okt.item())
+        if full:
+            okt = torch.tensor([1 if ok_roundtrip else 0], device=rdev)
+            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+            ok_roundtrip = bool(okt.item())
+
+    L = SHARD_LEN
+    enc_bytes = B * (k + m) * L                  # read k shards, write m shards
+    dec_bytes = B * (k + 1) * L                  # read first k present, write 1 erased data shard
+    value = shard.aggregate_gibps([B] * world, k, PAYLOAD, step_ms / 1000.0)
+    enc_bw = enc_bytes / (enc_ms / 1000.0)
+    dec_bw = dec_bytes / (dec_ms / 1000.0)
+
+    # what both forms of the result line share: the headline figure and its workload
+    head = {
+        "metric": "device-resident FEC encode+decode GiB/s, 1200B symbols, RS k=%d n=%d" % (k, n),
+        "value": round(value, 2),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "rank_ms_per_step": [round(x, 4) for x in rank_step_ms],
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_ms, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "full": full,
+        "outputs_dumped": args.dump_outputs,
+        "data": "synthetic: splitmix64 bytes keyed by (seed 0x%04X, global block, shard, word), "
+                "generated in HBM (include/fec_synth.h, BASELINE.md 2)" % args.seed,
+        "config": {"workload": "RS(k=%d,n=%d) encode + random single-data-erasure decode" % (k, n),
+                   "blocks_per_gpu": B, "payload_bytes": PAYLOAD, "shard_len": L,
+                   "shard_stride": SHARD_STRIDE, "layout": "data [B][k][1216] + parity [B][m][1216] buffers",
+                   "parallelism": "independent block ranges per GPU",
+                   "rehearsal": bool(args.rehearse_one_gpu and world > 1)},
+    }
+    if not full:
+        # the plain line: the headline figure and what the timed steps' own events say, nothing
+        # that takes a run of its own
+        if rank == 0:
+            head["kernels"] = {
+                "encode": {"ms": round(enc_ms, 4), "GB/s": round(enc_bw / 1e9, 1), "bytes": enc_bytes,
+                           "frac": round(enc_bw / HBM_PEAK, 4)},
+                "decode": {"ms": round(dec_ms, 4), "GB/s": round(dec_bw / 1e9, 1), "bytes": dec_bytes,
+                           "frac": round(dec_bw / HBM_PEAK, 4)},
+                "step_frac": round((enc_bytes + dec_bytes) / ((enc_ms + dec_ms) / 1000.0) / HBM_PEAK, 4)}
+            head["note"] = "plain run: checks, roofline, traffic twins, host-resident path and CPU baseline need --full"
+            print(json.dumps(head), flush=True)
+        codec.close()
+        if distributed:
+            dist.destroy_process_group()
+        return
 
     # 64 random blocks (data + parity) for the oracle spot-check, which runs in the cpu_baseline
     # leg (N = 1, rank 0): the only part of bench.py that touches oracle/. Otherwise None (not
@@ -597,16 +700,10 @@ def main():
         pick = torch.randperm(B, device=dev)[:64]
         parity_sample = torch.cat([batch.data[pick], batch.parity[pick]], dim=1).cpu().numpy()
 
-    L = SHARD_LEN
-    enc_bytes = B * (k + m) * L                  # read k shards, write m shards
-    dec_bytes = B * (k + 1) * L                  # read first k present, write 1 erased data shard
     # this box's ceiling for each kernel's access shape, after the checks (the twins overwrite the
     # parity and recovered buffers): traffic twins (include/fec_probe.h), interleaved with the
     # kernels themselves so both see the same box state
     probe = box_probe(torch, codec, batch, step, stream, enc_bytes, dec_bytes)
-    value = shard.aggregate_gibps([B] * world, k, PAYLOAD, step_ms / 1000.0)
-    enc_bw = enc_bytes / (enc_ms / 1000.0)
-    dec_bw = dec_bytes / (dec_ms / 1000.0)
     enc_kernel = encode_kernel_name(k, m)
     if enc_ms >= dec_ms:
         dom_name = "encode"
@@ -621,26 +718,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "device-resident FEC encode+decode GiB/s, 1200B symbols, RS k=%d n=%d" % (k, n),
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "ranks_seen": ranks_seen,
-            "rank_ms_per_step": [round(x, 4) for x in rank_step_ms],
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_ms, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic: splitmix64 bytes keyed by (seed 0x0FEC, global block, shard, word), "
-                    "generated in HBM (include/fec_synth.h, BASELINE.md 2)",
-            "config": {"workload": "RS(k=%d,n=%d) encode + random single-data-erasure decode" % (k, n),
-                       "blocks_per_gpu": B, "payload_bytes": PAYLOAD, "shard_len": L,
-                       "shard_stride": SHARD_STRIDE, "layout": "data [B][k][1216] + parity [B][m][1216] buffers",
-                       "parallelism": "independent block ranges per GPU",
-                       "rehearsal": bool(args.rehearse_one_gpu and world > 1)},
+            **head,
             "roofline": {"bound": "hbm", "achieved": round(dom_bw / 1e9, 1), "peak": HBM_PEAK / 1e9,
                          "unit": "GB/s", "frac": round(dom_bw / HBM_PEAK, 4),
                          "traffic": None if traffic is None else round(traffic / 1e9, 3),

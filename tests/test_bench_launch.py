@@ -31,6 +31,30 @@ def test_world_size_mismatch_is_refused():
     assert "WORLD_SIZE=2 but --gpus 4" in r.stderr
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for; --steps sets the timed steps and must
+    be at least 1 (ms_per_step divides by it)."""
+    import pytest
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", [BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", [BENCH, "--full", "--dump-outputs", "somewhere"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "somewhere"
+    monkeypatch.setattr(sys, "argv", [BENCH, "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_launcher_builds_a_torchrun_child(monkeypatch):
     """launch_ranks hands torchrun N ranks on 127.0.0.1 and this script, and returns its status."""
     import importlib.util

@@ -9,7 +9,7 @@
 #   tests       pytest -m gpu (the whole GPU suite)
 #   variants    pytest -m gpu -k kernel_variants / plan_forms (every shipped kernel path against the oracle)
 #   smoke       __graft_entry__.smoke()
-#   bench       bench.py (the contract line)
+#   bench       bench.py --full (the contract line with its checks, roofline, host path and CPU baseline)
 #   prof        rocprofv3 --kernel-trace --stats of bench.py -> kernel_trace_summary.json
 #   pmc         rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py -> pmc_traffic.json
 #   configs     tools/config_bench.py (every BASELINE config, device-resident)
@@ -46,7 +46,7 @@ for s in $STEPS; do
       timeout -k 10 120 python -u -c 'import __graft_entry__ as g; g.smoke()' > "$O/smoke.log" 2>&1
       tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$O/bench.log" 2>&1
+      timeout -k 10 300 python -u bench.py --full > "$O/bench.log" 2>&1
       tail -1 "$O/bench.log" ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run \
