@@ -337,7 +337,8 @@ static int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks
             a.div_cps = fk::make_fastdiv(cps);
             a.tabs = code->d_tabs + (size_t)r0 * k * 8;
             a.dytabs = (r0 == 0 && mr == code->m) ? code->d_dytabs : nullptr;
-            a.sp = fk::encode_store_policy(fk::g_tune.st_pol, data, dbs, parity, pbs, nblocks);
+            a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {data, dbs, ss, (uint64_t)k},
+                                           {parity, pbs, ss, (uint64_t)code->m}, len, nblocks);
             if (fk::fixed_encode_applies((uint32_t)k, (uint32_t)mr, a.dytabs != nullptr)) {
                 HIP_TRY(fk::launch_rs_encode_fixed(a, ctx->stream));
                 continue;
@@ -431,7 +432,8 @@ static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nb
             a.single = code->d_single;
             a.single_coef = code->d_single_coef;
             a.single_coef_host = code->single_coef.data();
-            a.sp = fk::decode_store_policy(fk::g_tune.dst_pol, data, dbs, parity, pbs, out, out_bs, nblocks);
+            a.sp = fk::decode_store_policy(fk::g_tune.dst_pol, {data, dbs, ss, k}, {parity, pbs, pss, m},
+                                           {out, out_bs, ss, out_slots}, len, nblocks);
         }
         if (direct) {
             HIP_TRY(fk::launch_rs_recover_direct(a, ctx->stream));
@@ -1267,6 +1269,63 @@ int fec__selftest_permtab(void) {
         if (a.t0lo != b.t0lo || a.t0hi != b.t0hi || a.t1lo != b.t1lo || a.t1hi != b.t1hi || a.t2 != b.t2)
             return 1 + (int)c;
     }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the store policy of a call
+// follows the hulls of its shard regions (fec_kernels.hpp regions_apart) for block-major and
+// shard-major layouts. Addresses are only compared, never dereferenced. 0 on success, else
+// 1 + the index of the first failing row.
+int fec__selftest_store_policy(void) {
+    const uint64_t S = 1216, L = 1202, B = 67, k = 8, m = 4;
+    const uintptr_t base = 0x10000000;
+    auto at = [&](uint64_t off) { return (const void*)(base + off); };
+    struct Row {
+        int st_pol;
+        fk::ShardRegion data, parity;
+        uint64_t nblocks;
+        uint32_t want;
+    };
+    const Row rows[] = {
+        // split, block-major [B][k][S] + [B][m][S]: apart (parity above data, and below it)
+        {1, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, B, 1u},
+        {1, {at(B * m * S), k * S, S, k}, {at(0), m * S, S, m}, B, 1u},
+        // (those two touch); one 16-byte chunk into each other
+        {1, {at(0), k * S, S, k}, {at(B * k * S - 16), m * S, S, m}, B, 0u},
+        // interleaved [B][k+m][S]: parity slots among the data
+        {1, {at(0), (k + m) * S, S, k}, {at(k * S), (k + m) * S, S, m}, B, 0u},
+        // one block of it: its parity lies past its data
+        {1, {at(0), (k + m) * S, S, k}, {at(k * S), (k + m) * S, S, m}, 1, 1u},
+        // shard-major [k+m][B][S] in one region: parity rows after the last data row
+        {1, {at(0), S, B * S, k}, {at(k * B * S), S, B * S, m}, B, 1u},
+        // shard-major, parity rows in the gaps between the data rows
+        {1, {at(0), S, 2 * B * S, k}, {at(B * S), S, 2 * B * S, m}, B, 0u},
+        // shard-major data, block-major parity inside the data's second row
+        {1, {at(0), S, B * S, k}, {at(B * S), m * S, S, m}, 8, 0u},
+        // no blocks: nothing to claim
+        {1, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, 0, 0u},
+        // knob values: 0 nt whatever the layout, 2 sc1 whatever the layout
+        {0, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, B, 0u},
+        {2, {at(0), (k + m) * S, S, k}, {at(k * S), (k + m) * S, S, m}, B, 1u},
+        {2, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, 0, 1u},
+    };
+    int i = 0;
+    for (const Row& r : rows) {
+        ++i;
+        if (fk::encode_store_policy(r.st_pol, r.data, r.parity, L, r.nblocks) != r.want) return i;
+        // symmetric in its two regions
+        if (fk::encode_store_policy(r.st_pol, r.parity, r.data, L, r.nblocks) != r.want) return i;
+    }
+    // decode: nt sc1 (3) only into an out region apart from both the data and the parity read
+    const fk::ShardRegion d{at(0), S, B * S, k}, p{at(k * B * S), S, B * S, m};
+    const fk::ShardRegion out_far{at((k + m) * B * S), S, B * S, m}, out_in_parity{at((k + 1) * B * S), S, B * S, 1};
+    const fk::ShardRegion out_rows_over_data{at(B * S - 16 * S), 16 * S, S, m}, none{nullptr, 0, 0, 0};
+    if (fk::decode_store_policy(3, d, p, out_far, L, B) != 3u) return 101;
+    if (fk::decode_store_policy(3, d, p, out_in_parity, L, B) != 0u) return 102;
+    if (fk::decode_store_policy(3, d, p, out_rows_over_data, L, B) != 0u) return 103;
+    if (fk::decode_store_policy(3, d, p, none, L, B) != 0u) return 104;       // in place
+    if (fk::decode_store_policy(0, d, p, out_far, L, B) != 0u) return 105;    // knob: nt
+    if (fk::decode_store_policy(3, d, p, out_far, L, 0) != 0u) return 106;
     return 0;
 }
 

@@ -39,22 +39,33 @@ struct EncodeArgs {
 // The encodes' store policy for a call (knob st_pol): sc1 stores let parity lines leave the XCD's L2
 // (-1.4 to -2.1 % RS(8,12) encode time on split buffers), but into parity slots interleaved with the
 // data being read ([B][k+m][S]) they cost 26 % (the XOR layout's twin, r06h): so sc1 only when the
-// [lo, hi) ranges of the two regions do not meet.
-inline bool regions_apart(const void* a, uint64_t abs, const void* b, uint64_t bbs, uint64_t nblocks) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + abs * nblocks, b0 = (uintptr_t)b, b1 = b0 + bbs * nblocks;
+// [lo, hi) ranges of the two regions do not meet. A region is the hull of its shard slots: `rows`
+// shards per block, `ss` apart, in nblocks blocks `bs` apart, each `len` bytes rounded up to the
+// 16-byte chunk the kernels move: [base, base + (nblocks-1)*bs + (rows-1)*ss + rup16(len)). That
+// holds for block-major ([B][rows][S]) and shard-major ([rows][B][S]) layouts alike; two regions
+// whose rows alternate (parity rows in the gaps between shard-major data rows) have meeting hulls.
+struct ShardRegion {
+    const void* base;
+    uint64_t bs, ss, rows;
+};
+inline bool regions_apart(const ShardRegion& a, const ShardRegion& b, uint64_t len, uint64_t nblocks) {
+    if (nblocks == 0 || a.rows == 0 || b.rows == 0) return false;   // no region: no claim
+    const uint64_t ext = (len + kChunk - 1) / kChunk * kChunk;
+    const uintptr_t a0 = (uintptr_t)a.base, a1 = a0 + (nblocks - 1) * a.bs + (a.rows - 1) * a.ss + ext;
+    const uintptr_t b0 = (uintptr_t)b.base, b1 = b0 + (nblocks - 1) * b.bs + (b.rows - 1) * b.ss + ext;
     return b1 <= a0 || a1 <= b0;
 }
-inline uint32_t encode_store_policy(int st_pol, const void* data, uint64_t dbs, const void* parity, uint64_t pbs,
+inline uint32_t encode_store_policy(int st_pol, const ShardRegion& data, const ShardRegion& parity, uint64_t len,
                                     uint64_t nblocks) {
     // (st_pol 2: sc1 whatever the layout, measurement only)
-    return st_pol == 2 || (st_pol == 1 && nblocks && regions_apart(data, dbs, parity, pbs, nblocks)) ? 1u : 0u;
+    return st_pol == 2 || (st_pol == 1 && regions_apart(data, parity, len, nblocks)) ? 1u : 0u;
 }
 // The RS(8,12) direct decode's (knob dst_pol): nt sc1 only into an output region apart from the
 // shards it reads (recover calls), else nt (in place: the rebuilt shard lands among the data).
-inline uint32_t decode_store_policy(int dst_pol, const void* data, uint64_t dbs, const void* parity, uint64_t pbs,
-                                    const void* out, uint64_t obs, uint64_t nblocks) {
-    return dst_pol == 3 && out && nblocks && regions_apart(data, dbs, out, obs, nblocks) &&
-                   regions_apart(parity, pbs, out, obs, nblocks)
+inline uint32_t decode_store_policy(int dst_pol, const ShardRegion& data, const ShardRegion& parity,
+                                    const ShardRegion& out, uint64_t len, uint64_t nblocks) {
+    return dst_pol == 3 && out.base && regions_apart(data, out, len, nblocks) &&
+                   regions_apart(parity, out, len, nblocks)
                ? 3u
                : 0u;
 }

@@ -222,7 +222,8 @@ extern "C" int fec_probe_encode_traffic(fec_ctx* ctx, int k, int m, size_t shard
     if (wpc < 0) wpc = k >= 16 ? (int)g_tune.enc_bwpc : k == 2 ? 0 : (int)g_tune.enc_wpc;
     const size_t lds = occupancy_lds(wpc, k == 8 ? (size_t)m * k * 32 : 0);
     // the encodes' store policy for this layout (encode_store_policy)
-    a.sp = encode_store_policy(g_tune.st_pol, data, dbs, parity, pbs, nblocks);
+    a.sp = encode_store_policy(g_tune.st_pol, {data, dbs, ss, (uint64_t)k}, {parity, pbs, ss, (uint64_t)m}, shard_len,
+                               nblocks);
 #define FEC_ENC_TWIN(K, M)                                                                              \
     do {                                                                                                \
         if (a.sp == 1)                                                                                  \
@@ -274,7 +275,8 @@ extern "C" int fec_probe_recover_traffic(fec_ctx* ctx, int k, int m, size_t shar
     const size_t lds = occupancy_lds(wpc, (size_t)4 * 3 * k * 32);
     const uint32_t um = (uint32_t)m;
     if (k == 2) hipLaunchKernelGGL((probe_recover_kernel<2>), dim3(grid), dim3(kThreads), lds, s, a, um);
-    else if (k == 8 && decode_store_policy(g_tune.dst_pol, data, dbs, parity, pbs, out, out_bs, nblocks) == 3)
+    else if (k == 8 && decode_store_policy(g_tune.dst_pol, {data, dbs, ss, (uint64_t)k}, {parity, pbs, ss, (uint64_t)m},
+                                           {out, out_bs, ss, 1}, shard_len, nblocks) == 3)
         hipLaunchKernelGGL((probe_recover_kernel<8, 3>), dim3(grid), dim3(kThreads), lds, s, a, um);
     else if (k == 8) hipLaunchKernelGGL((probe_recover_kernel<8>), dim3(grid), dim3(kThreads), lds, s, a, um);
     else if (k == 16) hipLaunchKernelGGL((probe_recover_kernel<16>), dim3(grid), dim3(kThreads), lds, s, a, um);

@@ -146,8 +146,11 @@ int fec_rs_reconstruct_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_
  * as fec_rs_reconstruct_batch) into  out + b*out_block_stride + r*shard_stride, r = 0..e-1,
  * in ascending shard order; data and parity are only read. out_slots = shard slots per block
  * in `out`. block_status (optional) receives e (>= 0) or FEC_ERR_TOO_FEW_SHARDS, or
- * FEC_ERR_INVALID_ARG when e > out_slots (that block is not written). FEC_DEVICE only;
- * fec_sync() reports any failed block. */
+ * FEC_ERR_INVALID_ARG when e > out_slots (that block is not written). An out slot is an output
+ * shard slot like any other: slots r < e of a block that succeeds receive bytes [0, shard_len)
+ * and zeros up to round_up(shard_len, 16); slots r >= e, the slots of a block that fails or has
+ * nothing erased, and every byte outside the slots' first round_up(shard_len, 16) bytes are not
+ * touched. FEC_DEVICE only; fec_sync() reports any failed block. */
 int fec_rs_recover_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
                          const uint8_t *data, size_t data_block_stride,
                          const uint8_t *parity, size_t parity_block_stride,

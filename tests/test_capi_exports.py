@@ -81,3 +81,12 @@ def test_copy_workers_cover_every_index_once(fec):
     # sanitized CPU run repeats it under ASan / UBSan)
     lib = ctypes.CDLL(fec._LIB_PATH)
     assert lib.fec__selftest_copypool() == 0
+
+
+def test_store_policy_follows_region_hulls(fec):
+    # sc1 stores only into a parity (or out) region apart from the shards read: the library's
+    # table of layouts (fec_capi.cpp fec__selftest_store_policy): split block-major and
+    # shard-major in one region apart, interleaved and row-alternating shard-major not, empty
+    # batches nt, knob st_pol 2 sc1 always (no device needed: addresses are only compared)
+    lib = ctypes.CDLL(fec._LIB_PATH)
+    assert lib.fec__selftest_store_policy() == 0
