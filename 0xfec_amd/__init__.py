@@ -49,6 +49,7 @@ FEC_DEVICE = 0
 FEC_HOST = 1
 FEC_HOST_PINNED = 2
 FEC_MAX_DECODE_SHARDS = 32
+FEC_MAX_WIDE_SHARDS = 256
 
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -72,6 +73,9 @@ lib.fec_rs_prepare.argtypes = [_vp, _i, _i]
 lib.fec_rs_encode_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_rs_reconstruct_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_recover_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _i, _vp, _i]
+lib.fec_rs_reconstruct_wide_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _i]
+lib.fec_rs_recover_wide_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _i, _vp,
+                                          _i]
 lib.fec_xor_encode_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_xor_reconstruct_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 _u64 = ctypes.c_uint64
@@ -113,6 +117,23 @@ def rs_matrix(k, m):
     out = np.zeros((k + m, k), dtype=np.uint8)
     _check(lib.fec_rs_matrix(k, m, out.ctypes.data), "fec_rs_matrix")
     return out
+
+
+def mask_words(n):
+    """FEC_MASK_WORDS: the uint32 words a present mask over n shards takes (1..8)."""
+    return (n + 31) // 32
+
+
+def wide_masks(present):
+    """bool [B, n] (shard i of block b present) -> uint32 [B, mask_words(n)] numpy array: shard i is
+    bit i % 32 of word i // 32, the form the wide calls take."""
+    import numpy as np
+    present = np.asarray(present, dtype=bool)
+    B, n = present.shape
+    W = mask_words(n)
+    bits = np.zeros((B, W * 32), dtype=np.uint8)
+    bits[:, :n] = present
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u4").reshape(B, W)
 
 
 def _addr(x):
@@ -290,6 +311,62 @@ class Codec:
         rc = self.rs_recover_raw(k, m, L, B, _addr(data)[0], k * S, _addr(parity)[0], m * S, S, _addr(masks)[0],
                                  _addr(out)[0], slots * S, slots, sa)
         return _check(rc, "fec_rs_recover_batch")
+
+    # ---- wide forms (k + m <= 256): masks are uint32 [B, W] arrays, FEC_MASK_WORDS(k + m) <= W <= 8,
+    # living where the shards live; same return conventions as the narrow methods
+    def rs_reconstruct_wide_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks, mask_words,
+                                status, flags):
+        return lib.fec_rs_reconstruct_wide_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                                 masks, mask_words, status, flags)
+
+    def rs_recover_wide_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks, mask_words, out,
+                            out_bs, out_slots, status, flags=FEC_DEVICE):
+        return lib.fec_rs_recover_wide_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks,
+                                             mask_words, out, out_bs, out_slots, status, flags)
+
+    @staticmethod
+    def _mask_shape(masks, B):
+        assert len(masks.shape) == 2 and masks.shape[0] == B, "wide masks are [B, W]"
+        if hasattr(masks, "is_contiguous"):
+            assert masks.is_contiguous() and masks.element_size() == 4
+        else:
+            assert masks.flags.c_contiguous and masks.itemsize == 4
+        return int(masks.shape[1])
+
+    def rs_reconstruct_wide(self, k, m, shards, masks, status=None, shard_len=None):
+        """Returns the C return code (FEC_OK or FEC_ERR_TOO_FEW_SHARDS for FEC_HOST)."""
+        B, n, S = _shape3(shards)
+        assert n == k + m
+        W = self._mask_shape(masks, B)
+        a, kind = _addr(shards)
+        fn = lambda B_, L, d, dbs, p, pbs, ss, ma, sa, kd: lib.fec_rs_reconstruct_wide_batch(
+            self._h, k, m, L, B_, d, dbs, p, pbs, ss, ma, W, sa, kd)
+        return self._recon(fn, "fec_rs_reconstruct_wide_batch", k, m, B, S, a, n * S, a + k * S, n * S, kind,
+                           masks, status, shard_len)
+
+    def rs_reconstruct_wide_split(self, k, m, data, parity, masks, status=None, shard_len=None):
+        B, kk, S = _shape3(data)
+        assert kk == k and tuple(parity.shape) == (B, m, S)
+        W = self._mask_shape(masks, B)
+        d, kind = _addr(data)
+        p, _ = _addr(parity)
+        fn = lambda B_, L, d_, dbs, p_, pbs, ss, ma, sa, kd: lib.fec_rs_reconstruct_wide_batch(
+            self._h, k, m, L, B_, d_, dbs, p_, pbs, ss, ma, W, sa, kd)
+        return self._recon(fn, "fec_rs_reconstruct_wide_batch", k, m, B, S, d, k * S, p, m * S, kind,
+                           masks, status, shard_len)
+
+    def rs_recover_wide_split(self, k, m, data, parity, masks, out, status=None, shard_len=None):
+        """Rebuild the erased data shards of each block into out [B, slots, S] (ascending order);
+        status[b] = number rebuilt, or a negative error code."""
+        B, kk, S = _shape3(data)
+        B2, slots, S2 = _shape3(out)
+        assert kk == k and tuple(parity.shape) == (B, m, S) and (B2, S2) == (B, S)
+        W = self._mask_shape(masks, B)
+        L = S if shard_len is None else shard_len
+        sa = _addr(status)[0] if status is not None else None
+        rc = self.rs_recover_wide_raw(k, m, L, B, _addr(data)[0], k * S, _addr(parity)[0], m * S, S,
+                                      _addr(masks)[0], W, _addr(out)[0], slots * S, slots, sa)
+        return _check(rc, "fec_rs_recover_wide_batch")
 
     # ---- synthetic workload on the device (include/fec_synth.h; same bytes as shard.py)
     def synth_data(self, seed, first_block, nblocks, k, payload_len, data, block_stride, shard_stride):

@@ -22,6 +22,7 @@
 
 #include "../../include/fec_hip.h"
 #include "fec_kernels.hpp"
+#include "fec_wide.hpp"
 #include "gf256.h"
 #include "rs_matrix.hpp"
 
@@ -450,6 +451,67 @@ static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nb
             HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
             HIP_TRY(fk::launch_rs_reconstruct(a, (int)std::max<uint32_t>(1, a.ntiles), ctx->stream));
         }
+    }
+    return FEC_OK;
+}
+
+// Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
+// up to 256 shards. Plan records of the whole slice, then the tiled rebuild; batches are cut into
+// launches under kPlanBytes of records and kMaxItems items, as above.
+static int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
+                                      size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
+                                      const uint32_t* masks, size_t mask_words, int32_t* status, int* err,
+                                      uint8_t* out = nullptr, size_t out_bs = 0, uint32_t out_slots = 0) {
+    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
+    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
+    if (out) rows = std::min(rows, out_slots);
+    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
+    const fk::WideLayout lay = fk::wide_layout(k, rows);
+    size_t per_launch = std::min<size_t>(kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
+    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
+    const int rc = grow_plans(ctx, per_launch * lay.stride);
+    if (rc) return rc;
+    uint32_t G, C, TK;
+    fk::wide_tile_shape(cps, k, &G, &C, &TK);
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const size_t nb = std::min(per_launch, nblocks - b0);
+        fk::WidePlanArgs p{};
+        p.masks = masks + b0 * mask_words;
+        p.mask_words = (uint32_t)mask_words;
+        p.plans = ctx->work->d_plans;
+        p.status = status ? status + b0 : nullptr;
+        p.err = err;
+        p.k = k;
+        p.n = k + m;
+        p.nblocks = (uint32_t)nb;
+        p.rows = rows;
+        p.max_out = out ? out_slots : 0;
+        p.lay = lay;
+        p.div_k = fk::make_fastdiv(k);
+        fk::WideReconArgs a{};
+        a.data = data + b0 * dbs;
+        a.parity = parity + b0 * pbs;
+        a.dbs = dbs;
+        a.pbs = pbs;
+        a.ss = (uint32_t)ss;
+        a.plans = ctx->work->d_plans;
+        a.lay = lay;
+        a.k = k;
+        a.len = (uint32_t)len;
+        a.cps = cps;
+        a.nblocks = (uint32_t)nb;
+        a.g = G;
+        a.c = C;
+        a.tk = TK;
+        a.nctiles = (cps + C - 1) / C;
+        a.ntiles = (uint32_t)((nb + G - 1) / G) * a.nctiles;
+        a.div_c = fk::make_fastdiv(C);
+        a.div_nct = fk::make_fastdiv(a.nctiles);
+        a.out = out ? out + b0 * out_bs : nullptr;
+        a.out_bs = out_bs;
+        HIP_TRY(fk::launch_rs_plan_wide(p, ctx->stream));
+        HIP_TRY(fk::launch_rs_rebuild_wide(a, ctx->stream));
     }
     return FEC_OK;
 }
@@ -1047,6 +1109,53 @@ static int host_reconstruct_xor(fec_ctx* ctx, int k, size_t len, size_t nblocks,
     return err ? FEC_ERR_TOO_FEW_SHARDS : FEC_OK;
 }
 
+// FEC_HOST wide RS reconstruct: the plain form (it exists so that the scheme layer decodes wide
+// codes; it is PCIe-bound, and not pipelined). Each slice of blocks goes as [block][k+m][ssd]
+// through the ctx's pinned and device stage, is rebuilt in place on the device, and the rebuilt
+// data shards of the blocks that succeeded are copied back.
+static int host_reconstruct_wide(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                                 const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                                 size_t mask_words, int32_t* block_status) {
+    const size_t ssd = round16(len);
+    const size_t n = (size_t)k + m;
+    const size_t chunk = host_chunk_blocks(nblocks, n * ssd);
+    int rc;
+    if ((rc = grow_stage(ctx, chunk * n * ssd))) return rc;
+    if ((rc = grow_masks(ctx, chunk * mask_words))) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_err + 1, 0, sizeof(int), ctx->stream));
+    auto present = [&](size_t b, size_t i) { return (masks[b * mask_words + i / 32] >> (i % 32)) & 1u; };
+    std::vector<int32_t> st;
+    bool failed = false;
+    for (size_t b0 = 0; b0 < nblocks; b0 += chunk) {
+        const size_t nb = std::min(chunk, nblocks - b0);
+        for (size_t b = 0; b < nb; ++b)
+            for (size_t i = 0; i < n; ++i)
+                if (present(b0 + b, i))
+                    memcpy(ctx->h_stage + (b * n + i) * ssd,
+                           i < (size_t)k ? data + (b0 + b) * dbs + i * ss : parity + (b0 + b) * pbs + (i - k) * ss, len);
+        HIP_TRY(hipMemcpyAsync(ctx->d_masks, masks + b0 * mask_words, nb * mask_words * 4, hipMemcpyHostToDevice,
+                               ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->d_stage, ctx->h_stage, nb * n * ssd, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = rs_reconstruct_wide_device(ctx, k, m, len, nb, ctx->d_stage, n * ssd, ctx->d_stage + k * ssd, n * ssd,
+                                             ssd, ctx->d_masks, mask_words, ctx->d_status, ctx->d_err + 1)))
+            return rc;
+        st.resize(nb);
+        HIP_TRY(hipMemcpyAsync(st.data(), ctx->d_status, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->h_stage, ctx->d_stage, nb * n * ssd, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t b = 0; b < nb; ++b) {
+            if (block_status) block_status[b0 + b] = st[b];
+            if (st[b] != 0) {
+                failed = true;
+                continue;
+            }
+            for (size_t i = 0; i < (size_t)k; ++i)
+                if (!present(b0 + b, i)) memcpy(data + (b0 + b) * dbs + i * ss, ctx->h_stage + (b * n + i) * ssd, len);
+        }
+    }
+    return failed ? FEC_ERR_TOO_FEW_SHARDS : FEC_OK;
+}
+
 // ---------------------------------------------------------------- C ABI
 
 extern "C" {
@@ -1441,6 +1550,129 @@ int fec_rs_recover_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nb
     return rs_reconstruct_device(ctx, code, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
                                  parity, parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err,
                                  out, out_block_stride, (uint32_t)out_slots);
+}
+
+// Argument checks of the wide calls that need no device, in the narrow calls' order.
+static int check_wide_args(int k, int m, size_t shard_len, size_t mask_words, int flags, bool host_ok) {
+    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (k + m > FEC_MAX_WIDE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
+    if (flags != FEC_DEVICE && !(host_ok && (flags == FEC_HOST || flags == FEC_HOST_PINNED))) return FEC_ERR_INVALID_ARG;
+    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
+    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
+    if (mask_words < (size_t)FEC_MASK_WORDS(k + m) || mask_words > 8) return FEC_ERR_INVALID_ARG;
+    return FEC_OK;
+}
+
+int fec_rs_reconstruct_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
+                                  size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                                  size_t shard_stride, const uint32_t* present_mask, size_t mask_words,
+                                  int32_t* block_status, int flags) {
+    int rc = check_wide_args(k, m, shard_len, mask_words, flags, true);
+    if (rc) return rc;
+    if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)   // the narrow call, bytes and errors unchanged
+        return fec_rs_reconstruct_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
+                                        parity_block_stride, shard_stride, present_mask, block_status, flags);
+    if ((rc = select_device(ctx))) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0) return FEC_OK;
+    if (!data || !present_mask || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
+    if (m == 0) parity = data;   // never read: no parity slot exists
+    if (flags == FEC_DEVICE) {
+        if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
+        if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
+        if ((rc = check_device_words(present_mask, block_status))) return rc;
+        return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
+                                          parity_block_stride, shard_stride, present_mask, mask_words, block_status,
+                                          ctx->d_err);
+    }
+    return host_reconstruct_wide(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
+                                 shard_stride, present_mask, mask_words, block_status);
+}
+
+int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
+                              size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                              size_t shard_stride, const uint32_t* present_mask, size_t mask_words, uint8_t* out,
+                              size_t out_block_stride, int out_slots, int32_t* block_status, int flags) {
+    int rc = check_wide_args(k, m, shard_len, mask_words, flags, false);
+    if (rc) return rc;
+    if (out_slots <= 0) return FEC_ERR_INVALID_ARG;
+    if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)
+        return fec_rs_recover_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
+                                    parity_block_stride, shard_stride, present_mask, out, out_block_stride, out_slots,
+                                    block_status, flags);
+    if ((rc = select_device(ctx))) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0) return FEC_OK;
+    if (!data || !present_mask || !out || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
+    if (m == 0) parity = data;
+    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_layout(out, out_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_words(present_mask, block_status))) return rc;
+    return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
+                                      parity, parity_block_stride, shard_stride, present_mask, mask_words,
+                                      block_status, ctx->d_err, out, out_block_stride, (uint32_t)out_slots);
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the wide plan's coefficient
+// rows (fec_wide.hpp wide_logsum / wide_coef, the functions rs_plan_wide_kernel runs) equal the
+// rows of the inverse of the first-k-present submatrix of the systematic matrix, for 64 seeded
+// random recoverable masks per shape, plus all data lost where m >= k. 0 on success, else
+// 1000 * (shape index + 1) + mask index + 1.
+int fec__selftest_wide_plan(void) {
+    static const int shapes[][2] = {{32, 1}, {20, 13}, {33, 31}, {64, 16}, {128, 128}, {255, 1}, {1, 255}, {8, 4}};
+    uint8_t ex768[768];
+    for (uint32_t i = 0; i < 768; ++i) ex768[i] = fk::wide_exp768(i);
+    const uint8_t* lg = gf::kTables.log;
+    uint64_t seed = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const int k = sh[0], m = sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix(k, n);
+        if (M.empty()) return 1000 * si;
+        const int cases = 64 + (m >= k ? 1 : 0);
+        for (int ci = 0; ci < cases; ++ci) {
+            std::vector<uint8_t> pres((size_t)n, 1);
+            if (ci == 64) {
+                for (int i = 0; i < k; ++i) pres[i] = 0;
+            } else {
+                for (int lose = (int)(rnd() % (uint32_t)(m + 1)); lose > 0;) {
+                    const uint32_t i = rnd() % (uint32_t)n;
+                    if (pres[i]) {
+                        pres[i] = 0;
+                        --lose;
+                    }
+                }
+            }
+            std::vector<uint8_t> S, O;
+            for (int i = 0; i < n && (int)S.size() < k; ++i)
+                if (pres[i]) S.push_back((uint8_t)i);
+            for (int i = 0; i < k; ++i)
+                if (!pres[i]) O.push_back((uint8_t)i);
+            if (O.empty()) continue;
+            std::vector<uint8_t> sub((size_t)k * k);
+            for (int p = 0; p < k; ++p) memcpy(&sub[(size_t)p * k], &M[(size_t)S[p] * k], (size_t)k);
+            if (!rs::invert(k, sub.data())) return 1000 * si + ci + 1;
+            std::vector<uint32_t> D((size_t)k);
+            for (int p = 0; p < k; ++p) D[p] = fk::wide_logsum(lg, S.data(), (uint32_t)k, S[p], (uint32_t)p);
+            for (size_t r = 0; r < O.size(); ++r) {
+                const uint32_t N = fk::wide_logsum(lg, S.data(), (uint32_t)k, O[r], (uint32_t)k);
+                for (int p = 0; p < k; ++p)
+                    if (fk::wide_coef(ex768, lg, N, D[p], O[r], S[p]) != sub[(size_t)O[r] * k + p])
+                        return 1000 * si + ci + 1;
+            }
+        }
+    }
+    return 0;
 }
 
 int fec_xor_encode_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, const uint8_t* data,

@@ -259,20 +259,20 @@ Error ReedSolomonScheme::stageRecoverInput(Block& b, uint8_t* dst, size_t stride
         ++present;
     }
     if (present < k_) return codec_error(FEC_ERR_TOO_FEW_SHARDS);
-    // the device decode takes uint32 present masks: n <= 32 (klauspost itself reconstructs up
-    // to 256 shards; every code the reference builds has n <= 30, manager.go:54-90)
-    if (nsh > FEC_MAX_DECODE_SHARDS) return codec_error(FEC_ERR_MAX_SHARD_NUM);
-    uint32_t mask = 0;
+    // the present mask in words of 32 shards (nsh = k + m <= 256, checked by New): one word for the
+    // narrow device decode (n <= 32), up to eight for the wide one
+    uint32_t words[8] = {};
     for (int i = 0; i < nsh; ++i)
-        if (!shards[i].nil() && shards[i].len != 0) mask |= 1u << i;
+        if (!shards[i].nil() && shards[i].len != 0) words[i >> 5] |= 1u << (i & 31);
     if (L > stride) return Error::text(fmt("shard len (%zu) exceeds the staging slot (%zu)", L, stride));
     for (int i = 0; i < nsh; ++i)
-        if (mask >> i & 1u) {
+        if (words[i >> 5] >> (i & 31) & 1u) {
             memcpy(dst + (size_t)i * stride, shards[i].data(), L);
             memset(dst + (size_t)i * stride + L, 0, std::min(stride, (L + 15) & ~(size_t)15) - L);
         }
     plan->len = L;
-    plan->mask = mask;
+    memcpy(plan->words, words, sizeof(words));
+    plan->mask = words[0];
     return Error::nil();
 }
 
@@ -313,7 +313,7 @@ Error ReedSolomonScheme::stageRecoverPayloads(int biggest, const uint8_t* const*
     for (int i = 0; i < nsh && !L; ++i) L = len_of(i);
     if (L == 0) return codec_error(FEC_ERR_SHARD_NO_DATA);
     int present = 0;
-    uint32_t mask = 0;
+    uint32_t words[8] = {};
     for (int i = 0; i < nsh; ++i) {
         const size_t li = len_of(i);
         if (li == 0) continue;
@@ -321,12 +321,11 @@ Error ReedSolomonScheme::stageRecoverPayloads(int biggest, const uint8_t* const*
         ++present;
     }
     if (present < k_) return codec_error(FEC_ERR_TOO_FEW_SHARDS);
-    if (nsh > FEC_MAX_DECODE_SHARDS) return codec_error(FEC_ERR_MAX_SHARD_NUM);
     if (L > stride) return Error::text(fmt("shard len (%zu) exceeds the staging slot (%zu)", L, stride));
     const size_t pad = std::min(stride, (L + 15) & ~(size_t)15) - L;
     for (int i = 0; i < nsh; ++i) {
         if (len_of(i) == 0) continue;
-        mask |= 1u << i;
+        words[i >> 5] |= 1u << (i & 31);
         if (skip && skip[i]) continue;
         uint8_t* d = dst + (size_t)i * stride;
         if (i < k_) {   // payload[:shardLen] of a zeroed packet buffer, BE16 length at [biggest]
@@ -341,7 +340,8 @@ Error ReedSolomonScheme::stageRecoverPayloads(int biggest, const uint8_t* const*
         memset(d + L, 0, pad);
     }
     plan->len = L;
-    plan->mask = mask;
+    memcpy(plan->words, words, sizeof(words));
+    plan->mask = words[0];
     return Error::nil();
 }
 
@@ -381,10 +381,15 @@ Error ReedSolomonScheme::recoverSymbolPayloads(Block& b, Slice* out) {   // reed
     fec_ctx* ctx = nullptr;
     e = engine_->ctx(&ctx);
     if (!e.ok()) return e;
-    uint32_t mask = plan.mask;
     int32_t st = 0;
-    const int rc = fec_rs_reconstruct_batch(ctx, k_, m_, L, 1, dense.data(), (size_t)nsh * L, dense.data() + (size_t)k_ * L,
-                                            (size_t)nsh * L, L, &mask, &st, FEC_HOST);
+    // n <= 32: the narrow entry (one mask word); wider codes: the wide one
+    const int rc = nsh <= FEC_MAX_DECODE_SHARDS
+                       ? fec_rs_reconstruct_batch(ctx, k_, m_, L, 1, dense.data(), (size_t)nsh * L,
+                                                  dense.data() + (size_t)k_ * L, (size_t)nsh * L, L, plan.words, &st,
+                                                  FEC_HOST)
+                       : fec_rs_reconstruct_wide_batch(ctx, k_, m_, L, 1, dense.data(), (size_t)nsh * L,
+                                                       dense.data() + (size_t)k_ * L, (size_t)nsh * L, L, plan.words,
+                                                       (size_t)FEC_MASK_WORDS(nsh), &st, FEC_HOST);
     if (rc) return codec_error(rc);
     std::vector<const uint8_t*> rebuilt;
     for (int i : plan.missing) rebuilt.push_back(&dense[(size_t)i * L]);

@@ -16,6 +16,9 @@
  *   fec_rs_reconstruct_batch    Encoder.ReconstructData     internal/fec/reed_solomon.go:124
  *   fec_rs_recover_batch        ReconstructData + the copy-out of recoverSymbolPayloads
  *                                                           internal/fec/reed_solomon.go:124-133
+ *   fec_rs_reconstruct_wide_batch, fec_rs_recover_wide_batch
+ *                               the same two for every code klauspost accepts (k + m <= 256),
+ *                               present masks of 1..8 words per block
  *   fec_xor_encode_batch        xorScheme.xor loop          internal/fec/xor.go:28-33,44-56
  *   fec_xor_reconstruct_batch   xorScheme recover loops     internal/fec/xor.go:80-86
  *
@@ -49,6 +52,13 @@
  *               one 2D DMA between the caller's layout and the device. fec_rs_recover_batch
  *               is FEC_DEVICE only.
  *
+ * Shard limits. Encode takes every code klauspost accepts, k + m <= 256. The narrow decode calls
+ * (fec_rs_reconstruct_batch, fec_rs_recover_batch, fec_xor_reconstruct_batch) take one uint32
+ * present mask per block and so k + m <= FEC_MAX_DECODE_SHARDS = 32; they run the tuned kernels.
+ * The wide decode calls take FEC_MASK_WORDS(k + m)..8 mask words per block and decode every code
+ * the library encodes, k + m <= FEC_MAX_WIDE_SHARDS = 256. A wide call with k + m <= 32 and one
+ * mask word is forwarded to the narrow call.
+ *
  * Threading: a ctx has one HIP stream and is used by one caller at a time (the
  * reference's manager is per connection and not thread-safe either: manager.go:41-48).
  * Use one ctx per device per host thread.
@@ -67,7 +77,7 @@ extern "C" {
 #define FEC_OK 0
 #define FEC_ERR_INVALID_ARG (-1)     /* null pointer, bad stride/length/flags */
 #define FEC_ERR_INV_SHARD_NUM (-2)   /* klauspost ErrInvShardNum: k <= 0 or m < 0 */
-#define FEC_ERR_MAX_SHARD_NUM (-3)   /* klauspost ErrMaxShardNum: k + m > 256 (decode: > 32) */
+#define FEC_ERR_MAX_SHARD_NUM (-3)   /* klauspost ErrMaxShardNum: k + m > 256 (narrow decode: > 32) */
 #define FEC_ERR_TOO_FEW_SHARDS (-4)  /* klauspost ErrTooFewShards */
 #define FEC_ERR_SHARD_SIZE (-5)      /* klauspost ErrShardSize */
 #define FEC_ERR_SHARD_NO_DATA (-6)   /* klauspost ErrShardNoData: shard_len == 0 */
@@ -81,8 +91,11 @@ extern "C" {
 #define FEC_HOST 1
 #define FEC_HOST_PINNED 2
 
-/* Largest n = k + m the reconstruct path accepts (present masks are uint32). */
+/* Largest n = k + m the narrow reconstruct calls accept (their present masks are one uint32). */
 #define FEC_MAX_DECODE_SHARDS 32
+/* Largest n = k + m the wide reconstruct calls accept, and the mask words a code of n shards needs. */
+#define FEC_MAX_WIDE_SHARDS 256
+#define FEC_MASK_WORDS(n) (((n) + 31) / 32)          /* 1..8 */
 
 typedef struct fec_ctx fec_ctx;
 
@@ -157,6 +170,31 @@ int fec_rs_recover_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nb
                          size_t shard_stride, const uint32_t *present_mask,
                          uint8_t *out, size_t out_block_stride, int out_slots,
                          int32_t *block_status, int flags);
+
+/* Wide forms of the two calls above: k >= 1, m >= 0, k + m <= FEC_MAX_WIDE_SHARDS. Block b's
+ * present mask is the mask_words words at present_mask + b*mask_words; shard i is present iff bit
+ * i % 32 of word i / 32 is set; bits at and above k + m are ignored. FEC_MASK_WORDS(k + m) <=
+ * mask_words <= 8, else FEC_ERR_INVALID_ARG. Everything else is as in the narrow calls: layout and
+ * alignment rules, whole-16-byte-chunk outputs with zero fill, every missing data shard rebuilt
+ * from the first k present shards in index order, missing parity and complete blocks untouched,
+ * statuses (0 / e, FEC_ERR_TOO_FEW_SHARDS, FEC_ERR_INVALID_ARG for e > out_slots) and the sticky
+ * word fec_sync() reports. With k + m <= 32 and mask_words == 1 the call is forwarded to the narrow
+ * one; every other call runs the wide kernels (a plan record of up to ~16.5 KiB per block, then a
+ * tiled rebuild). Reconstruct takes FEC_DEVICE and FEC_HOST (FEC_HOST_PINNED is treated as
+ * FEC_HOST); its host form is plain, not pipelined: slices of the batch are staged whole through
+ * pinned memory, rebuilt on the device and the rebuilt shards copied back, so it is PCIe-bound (it
+ * exists for the scheme layer's one-block recoveries). Recover is FEC_DEVICE only. */
+int fec_rs_reconstruct_wide_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                                  uint8_t *data, size_t data_block_stride,
+                                  const uint8_t *parity, size_t parity_block_stride,
+                                  size_t shard_stride, const uint32_t *present_mask, size_t mask_words,
+                                  int32_t *block_status, int flags);
+int fec_rs_recover_wide_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                              const uint8_t *data, size_t data_block_stride,
+                              const uint8_t *parity, size_t parity_block_stride,
+                              size_t shard_stride, const uint32_t *present_mask, size_t mask_words,
+                              uint8_t *out, size_t out_block_stride, int out_slots,
+                              int32_t *block_status, int flags);
 
 /* XOR(k, 1) encode: parity = XOR of the k data shards. */
 int fec_xor_encode_batch(fec_ctx *ctx, int k, size_t shard_len, size_t nblocks,

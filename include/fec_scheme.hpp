@@ -137,7 +137,8 @@ public:
     struct RecoverPlan {
         bool nothing = false;
         size_t len = 0;
-        uint32_t mask = 0;
+        uint32_t words[8] = {};   // present mask: shard i is bit i % 32 of word i / 32 (n <= 256)
+        uint32_t mask = 0;        // words[0], the narrow calls' one-word mask (n <= 32)
         std::vector<int> missing;   // ascending missing data shard indices
     };
     Error stageRecoverInput(Block& b, uint8_t* dst, size_t stride, RecoverPlan* plan);
