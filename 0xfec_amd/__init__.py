@@ -76,6 +76,10 @@ lib.fec_rs_recover_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, 
 lib.fec_rs_reconstruct_wide_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _i]
 lib.fec_rs_recover_wide_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _i, _vp,
                                           _i]
+lib.fec_rs_encode_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
+lib.fec_rs_reconstruct_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
+lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _i, _vp,
+                                            _i]
 lib.fec_xor_encode_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_xor_reconstruct_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 _u64 = ctypes.c_uint64
@@ -222,7 +226,7 @@ class Codec:
     TUNING_KEYS = {"enc_wpc": 0, "gen_wpc": 1, "dec_wpc": 2, "dir_wpc": 3, "enc_bwpc": 4, "enc_fixed": 5,
                    "dec_wave": 6, "dec_direct": 7, "host_chunk": 8, "host_threads": 9, "bat_zc": 10,
                    "dec_route": 11, "st_pol": 12, "dst_pol": 13,
-                   "route_wpc": 14, "route_ww": 15, "xor_wpc": 16, "enc_ww": 17}
+                   "route_wpc": 14, "route_ww": 15, "xor_wpc": 16, "enc_ww": 17, "rag_g": 18}
 
     def set_tuning(self, **knobs):
         """Set kernel-selection knobs; returns the previous values (pass them back to restore)."""
@@ -367,6 +371,85 @@ class Codec:
         rc = self.rs_recover_wide_raw(k, m, L, B, _addr(data)[0], k * S, _addr(parity)[0], m * S, S,
                                       _addr(masks)[0], W, _addr(out)[0], slots * S, slots, sa)
         return _check(rc, "fec_rs_recover_wide_batch")
+
+    # ---- ragged forms (FEC_DEVICE only): lens is a uint32 / int32 device tensor [B], block b's shard
+    # length in bytes (0: the block is skipped; > max_shard_len: status FEC_ERR_SHARD_SIZE);
+    # max_shard_len defaults to the slot size S. The raw mirrors return the C return code.
+    def rs_encode_ragged_raw(self, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss, lens, status=None,
+                             flags=FEC_DEVICE):
+        return lib.fec_rs_encode_ragged_batch(self._h, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                              lens, status, flags)
+
+    def rs_reconstruct_ragged_raw(self, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss, masks, lens,
+                                  status=None, flags=FEC_DEVICE):
+        return lib.fec_rs_reconstruct_ragged_batch(self._h, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                                   masks, lens, status, flags)
+
+    def rs_recover_ragged_raw(self, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss, masks, lens, out,
+                              out_bs, out_slots, status=None, flags=FEC_DEVICE):
+        return lib.fec_rs_recover_ragged_batch(self._h, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                               masks, lens, out, out_bs, out_slots, status, flags)
+
+    @staticmethod
+    def _lens_addr(lens, B):
+        assert tuple(lens.shape) == (B,) and lens.is_cuda and lens.is_contiguous() and lens.element_size() == 4, \
+            "block lengths are a uint32 / int32 device tensor [B]"
+        return lens.data_ptr()
+
+    @staticmethod
+    def _dev(x):
+        a, kind = _addr(x)
+        assert kind == FEC_DEVICE, "the ragged calls take device memory only"
+        return a
+
+    def rs_encode_ragged(self, k, m, shards, lens, status=None, max_shard_len=None):
+        B, n, S = _shape3(shards)
+        assert n == k + m
+        a = self._dev(shards)
+        L = S if max_shard_len is None else max_shard_len
+        sa = self._dev(status) if status is not None else None
+        return _check(self.rs_encode_ragged_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, self._lens_addr(lens, B),
+                                                sa), "fec_rs_encode_ragged_batch")
+
+    def rs_encode_ragged_split(self, k, m, data, parity, lens, status=None, max_shard_len=None):
+        B, kk, S = _shape3(data)
+        B2, mm, S2 = _shape3(parity)
+        assert (kk, mm, B, S) == (k, m, B2, S2)
+        L = S if max_shard_len is None else max_shard_len
+        sa = self._dev(status) if status is not None else None
+        return _check(self.rs_encode_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
+                                                self._lens_addr(lens, B), sa), "fec_rs_encode_ragged_batch")
+
+    def rs_reconstruct_ragged(self, k, m, shards, masks, lens, status=None, max_shard_len=None):
+        B, n, S = _shape3(shards)
+        assert n == k + m
+        a = self._dev(shards)
+        L = S if max_shard_len is None else max_shard_len
+        sa = self._dev(status) if status is not None else None
+        return _check(self.rs_reconstruct_ragged_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, self._dev(masks),
+                                                     self._lens_addr(lens, B), sa),
+                      "fec_rs_reconstruct_ragged_batch")
+
+    def rs_reconstruct_ragged_split(self, k, m, data, parity, masks, lens, status=None, max_shard_len=None):
+        B, kk, S = _shape3(data)
+        assert kk == k and tuple(parity.shape) == (B, m, S)
+        L = S if max_shard_len is None else max_shard_len
+        sa = self._dev(status) if status is not None else None
+        return _check(self.rs_reconstruct_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
+                                                     self._dev(masks), self._lens_addr(lens, B), sa),
+                      "fec_rs_reconstruct_ragged_batch")
+
+    def rs_recover_ragged_split(self, k, m, data, parity, masks, lens, out, status=None, max_shard_len=None):
+        """Rebuild the erased data shards of each block into out [B, slots, S] (ascending order);
+        status[b] = number rebuilt, or a negative error code."""
+        B, kk, S = _shape3(data)
+        B2, slots, S2 = _shape3(out)
+        assert kk == k and tuple(parity.shape) == (B, m, S) and (B2, S2) == (B, S)
+        L = S if max_shard_len is None else max_shard_len
+        sa = self._dev(status) if status is not None else None
+        return _check(self.rs_recover_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
+                                                 self._dev(masks), self._lens_addr(lens, B), self._dev(out),
+                                                 slots * S, slots, sa), "fec_rs_recover_ragged_batch")
 
     # ---- synthetic workload on the device (include/fec_synth.h; same bytes as shard.py)
     def synth_data(self, seed, first_block, nblocks, k, payload_len, data, block_stride, shard_stride):

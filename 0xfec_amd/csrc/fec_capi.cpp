@@ -22,6 +22,7 @@
 
 #include "../../include/fec_hip.h"
 #include "fec_kernels.hpp"
+#include "fec_ragged.hpp"
 #include "fec_wide.hpp"
 #include "gf256.h"
 #include "rs_matrix.hpp"
@@ -512,6 +513,121 @@ static int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, 
         a.out_bs = out_bs;
         HIP_TRY(fk::launch_rs_plan_wide(p, ctx->stream));
         HIP_TRY(fk::launch_rs_rebuild_wide(a, ctx->stream));
+    }
+    return FEC_OK;
+}
+
+// Ragged batches (fec_ragged.hip): block b's shards are lens[b] bytes long, at most max_len. Cut
+// into launches as the uniform calls are, with cps_max = the chunks of a shard of max_len bytes.
+static uint32_t ragged_encode_blocks(uint32_t cps_max) {
+    const int forced = fk::g_tune.rag_g;
+    // a tile of full-length blocks fills one window (kRagRounds rounds)
+    const uint32_t want = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps_max);
+    return fk::rag_clamp_blocks(want, cps_max);
+}
+
+static int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, const uint8_t* data,
+                                   size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* lens,
+                                   int32_t* status, int* err) {
+    const uint32_t cps = (uint32_t)((max_len + fk::kChunk - 1) / fk::kChunk);
+    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
+    const int k = code->k;
+    const uint32_t G = ragged_encode_blocks(cps);
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const size_t nb = std::min(per_launch, nblocks - b0);
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            const int mr = std::min(16, code->m - r0);
+            fk::RagEncodeArgs a{};
+            a.in = data + b0 * dbs;
+            a.out = parity + b0 * pbs + (size_t)r0 * ss;
+            a.in_bs = dbs;
+            a.out_bs = pbs;
+            a.ss = ss;
+            a.k = (uint32_t)k;
+            a.m = (uint32_t)mr;
+            a.max_len = (uint32_t)max_len;
+            a.nblocks = (uint32_t)nb;
+            a.g = G;
+            a.nwin = fk::rag_windows(G, cps);
+            a.lens = lens + b0;
+            a.status = status ? status + b0 : nullptr;
+            a.err = err;
+            a.report = r0 == 0;
+            a.tabs = code->d_tabs + (size_t)r0 * k * 8;
+            HIP_TRY(fk::launch_rs_encode_ragged(a, ctx->stream));
+        }
+    }
+    return FEC_OK;
+}
+
+// Plans in block order by rs_plan_kernel (they do not depend on the length), then the ragged tile
+// rebuild, which also overrides the status of oversize blocks.
+static int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, uint8_t* data,
+                                        size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
+                                        const uint32_t* masks, const uint32_t* lens, int32_t* status, int* err,
+                                        uint8_t* out = nullptr, size_t out_bs = 0, uint32_t out_slots = 0) {
+    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild takes 32-bit shard strides
+    const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
+    const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
+    const uint32_t cps = (uint32_t)((max_len + fk::kChunk - 1) / fk::kChunk);
+    const fk::PlanLayout lay = fk::plan_layout(k, maxe);
+    size_t per_launch = std::min<size_t>(kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
+    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
+    const int rc = grow_plans(ctx, per_launch * lay.stride);
+    if (rc) return rc;
+    // rows a block can need: the plan kernel gives a block with more erasures than slots no rows
+    const uint32_t rows = out ? std::min(maxe, out_slots) : maxe;
+    // Blocks per tile: as the encode's, so that a tile of full-length blocks fills one window, within
+    // what LDS holds. (pick_tile_blocks, the uniform tile form's choice, looks for the fewest blocks
+    // that fill the lanes of a full-length tile: RS(20,30) 3. A ragged tile has fewer items than
+    // that, and its fixed cost, two barriers for the prefix and one for the tables, is paid per
+    // tile. Measured, the rebuild is indifferent between the two within the run-to-run spread; the
+    // encode is 30-42 % slower at 3 blocks per tile: DESIGN.md 4b.)
+    const int forced = fk::g_tune.rag_g;
+    uint32_t G = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps);
+    G = fk::rag_clamp_blocks(std::min(G, fk::rag_recon_max_blocks(k, rows, lay)), cps);
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const size_t nb = std::min(per_launch, nblocks - b0);
+        fk::PlanArgs p{};
+        p.masks = masks + b0;
+        p.plans = ctx->work->d_plans;
+        p.status = status ? status + b0 : nullptr;
+        p.err = err;
+        p.prows = code->d_prows;
+        p.k = k;
+        p.m = m;
+        p.nblocks = (uint32_t)nb;
+        p.maxe = maxe;
+        p.lay = lay;
+        p.max_out = out ? out_slots : 0;
+        fk::RagReconArgs ra{};
+        fk::ReconArgs& a = ra.r;
+        a.data = data + b0 * dbs;
+        a.parity = parity + b0 * pbs;
+        a.dbs = dbs;
+        a.pbs = pbs;
+        a.ss = ss;
+        a.pss = ss;
+        a.plans = ctx->work->d_plans;
+        a.k = k;
+        a.len = (uint32_t)max_len;
+        a.cps = cps;
+        a.nblocks = (uint32_t)nb;
+        a.maxe = maxe;
+        a.lay = lay;
+        a.g = G;
+        a.ntiles = (uint32_t)((nb + G - 1) / G);
+        a.div_cps = fk::make_fastdiv(cps);
+        a.out = out ? out + b0 * out_bs : nullptr;
+        a.out_bs = out_bs;
+        a.status = p.status;
+        a.err = err;
+        ra.lens = lens + b0;
+        ra.max_len = (uint32_t)max_len;
+        ra.nwin = fk::rag_windows(G, cps);
+        ra.rows = rows;
+        HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
+        HIP_TRY(fk::launch_rs_reconstruct_ragged(ra, ctx->stream));
     }
     return FEC_OK;
 }
@@ -1331,7 +1447,7 @@ int fec__set_tuning(fec_ctx* ctx, int key, int value) {
                                                 &t.host_chunk, &t.host_threads, &t.bat_zc,     &t.dec_route,
                                                 &t.st_pol,     &t.dst_pol,    &t.route_wpc,
                                                 &t.route_ww,   &t.xor_wpc,
-                                                &t.enc_ww};
+                                                &t.enc_ww,     &t.rag_g};
     if (key < 0 || key >= fk::kTuningKeys) return FEC_ERR_INVALID_ARG;
     return slots[key]->exchange(value);
 }
@@ -1454,8 +1570,12 @@ int fec_sync(fec_ctx* ctx) {
     if (err) {
         HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream));
         // 1: a block with too few shards; 2: more erasures than output slots; 4: internal (the
-        // form-3 plan kernel's LDS-alignment guard)
-        return (err & 1) ? FEC_ERR_TOO_FEW_SHARDS : (err & 4) ? FEC_ERR_HIP : FEC_ERR_INVALID_ARG;
+        // form-3 plan kernel's LDS-alignment guard); 8: a ragged call met a block longer than its
+        // max_shard_len
+        return (err & 1)   ? FEC_ERR_TOO_FEW_SHARDS
+               : (err & 4) ? FEC_ERR_HIP
+               : (err & 2) ? FEC_ERR_INVALID_ARG
+                           : FEC_ERR_SHARD_SIZE;
     }
     return FEC_OK;
 }
@@ -1614,6 +1734,157 @@ int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
     return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
                                       parity, parity_block_stride, shard_stride, present_mask, mask_words,
                                       block_status, ctx->d_err, out, out_block_stride, (uint32_t)out_slots);
+}
+
+// ---------------------------------------------------------------- ragged batches
+// Host-side checks in the uniform calls' order, max_shard_len in place of shard_len.
+static int check_ragged_args(int k, int m, int max_n, size_t max_shard_len, int flags) {
+    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (k + m > max_n) return FEC_ERR_MAX_SHARD_NUM;
+    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
+    if (max_shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
+    if (max_shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
+    return FEC_OK;
+}
+
+int fec_rs_encode_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, const uint8_t* data,
+                               size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
+                               size_t shard_stride, const uint32_t* block_len, int32_t* block_status, int flags) {
+    int rc = check_ragged_args(k, m, 256, max_shard_len, flags);
+    if (rc) return rc;
+    if ((rc = select_device(ctx))) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0 || m == 0) return FEC_OK;
+    if (!data || !parity || !block_len) return FEC_ERR_INVALID_ARG;
+    if ((rc = check_device_layout(data, data_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_words(block_len, block_status))) return rc;
+    return rs_encode_ragged_device(ctx, code, max_shard_len, nblocks, data, data_block_stride, parity,
+                                   parity_block_stride, shard_stride, block_len, block_status, ctx->d_err);
+}
+
+int fec_rs_reconstruct_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, uint8_t* data,
+                                    size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                                    size_t shard_stride, const uint32_t* present_mask, const uint32_t* block_len,
+                                    int32_t* block_status, int flags) {
+    int rc = check_ragged_args(k, m, FEC_MAX_DECODE_SHARDS, max_shard_len, flags);
+    if (rc) return rc;
+    if ((rc = select_device(ctx))) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0) return FEC_OK;
+    if (!data || !present_mask || !block_len || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
+    if (m == 0) parity = data;   // never read: no parity slot exists
+    if ((rc = check_device_layout(data, data_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_words(present_mask, block_status))) return rc;
+    if ((rc = check_device_words(block_len, nullptr))) return rc;
+    return rs_reconstruct_ragged_device(ctx, code, max_shard_len, nblocks, data, data_block_stride, parity,
+                                        parity_block_stride, shard_stride, present_mask, block_len, block_status,
+                                        ctx->d_err);
+}
+
+int fec_rs_recover_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, const uint8_t* data,
+                                size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                                size_t shard_stride, const uint32_t* present_mask, const uint32_t* block_len,
+                                uint8_t* out, size_t out_block_stride, int out_slots, int32_t* block_status,
+                                int flags) {
+    int rc = check_ragged_args(k, m, FEC_MAX_DECODE_SHARDS, max_shard_len, flags);
+    if (rc) return rc;
+    if (out_slots <= 0) return FEC_ERR_INVALID_ARG;
+    if ((rc = select_device(ctx))) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0) return FEC_OK;
+    if (!data || !present_mask || !block_len || !out || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
+    if (m == 0) parity = data;
+    if ((rc = check_device_layout(data, data_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_layout(out, out_block_stride, shard_stride, max_shard_len))) return rc;
+    if ((rc = check_device_words(present_mask, block_status))) return rc;
+    if ((rc = check_device_words(block_len, nullptr))) return rc;
+    return rs_reconstruct_ragged_device(ctx, code, max_shard_len, nblocks, const_cast<uint8_t*>(data),
+                                        data_block_stride, parity, parity_block_stride, shard_stride, present_mask,
+                                        block_len, block_status, ctx->d_err, out, out_block_stride,
+                                        (uint32_t)out_slots);
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the item arithmetic of the
+// ragged kernels (fec_ragged.hpp), walked as the kernels walk it. For each row of a table of length
+// vectors and tile sizes, every workgroup's tile and window are taken, its rounds of 256 lanes
+// swept, and each item located in the tile's prefix: the items met, in order, must be exactly the
+// (block, chunk) pairs of the batch in order, chunk below the block's count, each once, none
+// missing; a window past its tile's item count must be empty, and no workgroup may run more than
+// kRagRounds rounds. 0 on success, else 100 * (row + 1) + the failing check.
+int fec__selftest_ragged_tiles(void) {
+    struct Row {
+        std::vector<uint32_t> lens;
+        uint32_t max_len, g;
+    };
+    const uint32_t W = fk::kRagWindow, K16 = (uint32_t)fk::kChunk;
+    std::vector<Row> rows;
+    rows.push_back({std::vector<uint32_t>(40, 0), 1202, 8});                        // all-zero tiles
+    {   // a zero run spanning a tile edge (blocks 5..10 of tiles of 8), an oversize block in it
+        std::vector<uint32_t> l = {1202, 1, 16, 17, 50, 0, 0, 0, 0, 1203, 0, 33, 1202, 0, 15, 1200, 0xFFFFFFFFu, 7};
+        rows.push_back({l, 1202, 8});
+        rows.push_back({l, 1202, 3});
+        rows.push_back({l, 1202, 1});
+        rows.push_back({l, 1202, 256});
+    }
+    rows.push_back({{1202}, 1202, 16});                                             // a single block
+    rows.push_back({{1}, 1202, 1});
+    for (int d = -1; d <= 1; ++d) {   // a tile's sum = a multiple of 256, one less, one more
+        rows.push_back({{16u * 200u, 0, 16u * (uint32_t)(56 + d), 16u * 256u}, 16u * 256u, 4});
+        rows.push_back({{16u * (uint32_t)(256 + d)}, 16u * 300u, 1});
+        rows.push_back({{16u * (W / 2), 16u * (uint32_t)((int)(W / 2) + d)}, 16u * W, 2});   // and of a window
+    }
+    rows.push_back({{70000, 1, 33333}, 70000, 1});                                  // several windows per tile
+    rows.push_back({{70000, 1, 33333}, 70000, 16});
+    rows.push_back({{5, 0, 1u << 30, 17}, 1u << 30, 64});                           // a 2^26-chunk shard
+    int row = 0;
+    for (const Row& r : rows) {
+        const int fail = 100 * ++row;
+        const uint32_t nblocks = (uint32_t)r.lens.size();
+        const uint32_t cps_max = (r.max_len + K16 - 1) / K16;
+        const uint32_t G = fk::rag_clamp_blocks(r.g, cps_max);
+        if (G < 1 || G > fk::kRagMaxTileBlocks || (uint64_t)G * cps_max > fk::kRagMaxTileItems) return fail + 1;
+        const uint32_t nwin = fk::rag_windows(G, cps_max);
+        if ((uint64_t)nwin * W < (uint64_t)G * cps_max) return fail + 2;
+        const uint32_t ntiles = (nblocks + G - 1) / G;
+        uint32_t nb = 0, nc = 0;   // the next (block, chunk) the walk must meet
+        auto skip_empty = [&] {
+            while (nb < nblocks && nc >= fk::rag_chunks(r.lens[nb], r.max_len)) ++nb, nc = 0;
+        };
+        std::vector<uint32_t> prefix(G + 1);
+        for (uint32_t wg = 0; wg < ntiles * nwin; ++wg) {
+            const fk::RagTile T = fk::rag_tile(wg, G, nwin, nblocks);
+            if (T.gt < 1 || T.gt > G || T.b0 + T.gt > nblocks || T.win >= nwin) return fail + 3;
+            prefix[0] = 0;
+            for (uint32_t g = 0; g < T.gt; ++g) prefix[g + 1] = prefix[g] + fk::rag_chunks(r.lens[T.b0 + g], r.max_len);
+            const uint32_t total = prefix[T.gt];
+            const fk::RagSpan sp = fk::rag_span(T.win, total);
+            if (sp.hi > total || sp.lo > sp.hi) return fail + 4;
+            if ((uint64_t)T.win * W >= total && sp.lo != sp.hi) return fail + 5;   // a window past the sum is empty
+            uint32_t rounds = 0;
+            for (uint32_t base = sp.lo; base < sp.hi; base += (uint32_t)fk::kThreads, ++rounds)
+                for (uint32_t lane = 0; lane < (uint32_t)fk::kThreads; ++lane) {
+                    const uint32_t t = base + lane;
+                    if (t >= sp.hi) continue;
+                    const uint32_t g = fk::rag_locate(prefix.data(), T.gt, t);
+                    if (g >= T.gt) return fail + 6;
+                    const uint32_t c = t - prefix[g];
+                    if (c >= fk::rag_chunks(r.lens[T.b0 + g], r.max_len)) return fail + 7;
+                    skip_empty();
+                    if (nb != T.b0 + g || nc != c) return fail + 8;   // in order: each pair once
+                    ++nc;
+                }
+            if (rounds > fk::kRagRounds) return fail + 9;
+        }
+        skip_empty();
+        if (nb != nblocks) return fail + 10;   // every pair met
+    }
+    return 0;
 }
 
 // Internal self-test (not part of the public ABI, no device needed): the wide plan's coefficient

@@ -199,8 +199,11 @@ struct Tuning {
     // waves per workgroup that take items in the RS(8,12) encode (3: the fourth stages its table
     // words and exits, 9 working waves per CU at 3 workgroups/CU, shard loads before the barrier; 4: all)
     std::atomic<int> enc_ww{3};
+    // ragged kernels (fec_ragged.hip), tests: blocks per tile of both, clamped to what LDS and the
+    // 32-bit item ids allow (0: a window's items / the chunks of a full-length shard)
+    std::atomic<int> rag_g{0};
 };
-constexpr int kTuningKeys = 18;   // fec__set_tuning keys 0..17, in the order above
+constexpr int kTuningKeys = 19;   // fec__set_tuning keys 0..18, in the order above
 
 // Dynamic LDS that caps residency at `wpc` workgroups per CU (160 KiB of LDS per CU on gfx950):
 // halfway between 160K/(wpc+1) and 160K/wpc, never below what the kernel itself needs.

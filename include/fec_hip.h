@@ -19,6 +19,10 @@
  *   fec_rs_reconstruct_wide_batch, fec_rs_recover_wide_batch
  *                               the same two for every code klauspost accepts (k + m <= 256),
  *                               present masks of 1..8 words per block
+ *   fec_rs_encode_ragged_batch, fec_rs_reconstruct_ragged_batch, fec_rs_recover_ragged_batch
+ *                               Encode / ReconstructData / the copy-out for a batch whose blocks
+ *                               each have their own shard length, as the reference's blocks do
+ *                               (2 + biggestSourceSymbolLenSoFar, reed_solomon.go:47,80)
  *   fec_xor_encode_batch        xorScheme.xor loop          internal/fec/xor.go:28-33,44-56
  *   fec_xor_reconstruct_batch   xorScheme recover loops     internal/fec/xor.go:80-86
  *
@@ -57,7 +61,8 @@
  * present mask per block and so k + m <= FEC_MAX_DECODE_SHARDS = 32; they run the tuned kernels.
  * The wide decode calls take FEC_MASK_WORDS(k + m)..8 mask words per block and decode every code
  * the library encodes, k + m <= FEC_MAX_WIDE_SHARDS = 256. A wide call with k + m <= 32 and one
- * mask word is forwarded to the narrow call.
+ * mask word is forwarded to the narrow call. The ragged calls follow the uniform ones: encode
+ * k + m <= 256, reconstruct and recover k + m <= 32.
  *
  * Threading: a ctx has one HIP stream and is used by one caller at a time (the
  * reference's manager is per connection and not thread-safe either: manager.go:41-48).
@@ -79,7 +84,7 @@ extern "C" {
 #define FEC_ERR_INV_SHARD_NUM (-2)   /* klauspost ErrInvShardNum: k <= 0 or m < 0 */
 #define FEC_ERR_MAX_SHARD_NUM (-3)   /* klauspost ErrMaxShardNum: k + m > 256 (narrow decode: > 32) */
 #define FEC_ERR_TOO_FEW_SHARDS (-4)  /* klauspost ErrTooFewShards */
-#define FEC_ERR_SHARD_SIZE (-5)      /* klauspost ErrShardSize */
+#define FEC_ERR_SHARD_SIZE (-5)      /* klauspost ErrShardSize; ragged calls: block_len[b] > max_shard_len */
 #define FEC_ERR_SHARD_NO_DATA (-6)   /* klauspost ErrShardNoData: shard_len == 0 */
 #define FEC_ERR_ALIGNMENT (-7)       /* FEC_DEVICE layout not 16-byte aligned, or a mask / status
                                         array not 4-byte aligned */
@@ -122,8 +127,9 @@ void *fec_ctx_stream(fec_ctx *ctx);
 int fec_ctx_release_staging(fec_ctx *ctx);
 /* Wait for the ctx stream. Returns FEC_ERR_TOO_FEW_SHARDS if any FEC_DEVICE reconstruct
  * since the last fec_sync met a block with fewer than k present shards, or
- * FEC_ERR_INVALID_ARG if a recover met a block with more erasures than output slots
- * (then clears it). */
+ * FEC_ERR_INVALID_ARG if a recover met a block with more erasures than output slots, or
+ * FEC_ERR_SHARD_SIZE if a ragged call met a block longer than its max_shard_len and neither of
+ * the other two happened (then clears it). */
 int fec_sync(fec_ctx *ctx);
 
 /* The n x k systematic matrix of RS(k, m) (n = k + m), row-major, host memory. No device
@@ -195,6 +201,55 @@ int fec_rs_recover_wide_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size
                               size_t shard_stride, const uint32_t *present_mask, size_t mask_words,
                               uint8_t *out, size_t out_block_stride, int out_slots,
                               int32_t *block_status, int flags);
+
+/* Ragged forms of fec_rs_encode_batch, fec_rs_reconstruct_batch and fec_rs_recover_batch: block b's
+ * shards are block_len[b] bytes long instead of one shard_len for the batch, and the kernels' work
+ * and memory traffic follow the sum of the blocks' lengths (in 16-byte chunks), not nblocks times the
+ * longest. FEC_DEVICE only: any other `flags` value returns FEC_ERR_INVALID_ARG.
+ *
+ * Layout and alignment. block_len is an array of nblocks uint32 in device memory, 4-byte aligned
+ * (else FEC_ERR_ALIGNMENT). Shard layout, strides and alignment are those of the uniform calls and
+ * are checked the same way with max_shard_len in place of shard_len (shard_stride >= max_shard_len;
+ * every slot readable over shard_stride bytes). max_shard_len == 0 returns FEC_ERR_SHARD_NO_DATA,
+ * max_shard_len > 2^30 FEC_ERR_INVALID_ARG. Encode takes k + m <= 256, the decode pair
+ * k + m <= FEC_MAX_DECODE_SHARDS with one uint32 present mask per block. The host-side checks run in
+ * the uniform calls' order (shard counts, flags, max_shard_len, out_slots, then the pointers,
+ * block_len among them, the layouts and the word alignment). Batches are cut into launches as the
+ * uniform calls cut them, with max_shard_len as the shard length.
+ *
+ * A block with 0 < block_len[b] <= max_shard_len is coded exactly as the uniform call would code it
+ * alone with shard_len = block_len[b]: bytes [0, len) of each output shard receive the result, bytes
+ * [len, round_up(len, 16)) are written as zeros, nothing else is written, and nothing at or past
+ * round_up(len, 16) of any input slot is read.
+ *
+ * A block with block_len[b] == 0 has no byte read or written; its status is what its mask gives.
+ *
+ * Statuses and the sticky word are what the uniform call gives for the same masks (reconstruct: 0
+ * or FEC_ERR_TOO_FEW_SHARDS; recover: e, FEC_ERR_TOO_FEW_SHARDS, or FEC_ERR_INVALID_ARG when
+ * e > out_slots); they do not depend on the length. The encode's block_status (optional) receives 0.
+ * (An encode with m == 0 or nblocks == 0 returns FEC_OK and does nothing, as the uniform one.)
+ *
+ * A block with block_len[b] > max_shard_len (a device-side value no host check can see) is neither
+ * read nor written; its status is FEC_ERR_SHARD_SIZE, whatever its mask, and fec_sync() returns
+ * FEC_ERR_SHARD_SIZE unless a too-few-shards or too-few-slots block is pending, which come first
+ * (the sticky word still records what the block's mask gives). */
+int fec_rs_encode_ragged_batch(fec_ctx *ctx, int k, int m, size_t max_shard_len, size_t nblocks,
+                               const uint8_t *data, size_t data_block_stride,
+                               uint8_t *parity, size_t parity_block_stride,
+                               size_t shard_stride, const uint32_t *block_len,
+                               int32_t *block_status, int flags);
+int fec_rs_reconstruct_ragged_batch(fec_ctx *ctx, int k, int m, size_t max_shard_len, size_t nblocks,
+                                    uint8_t *data, size_t data_block_stride,
+                                    const uint8_t *parity, size_t parity_block_stride,
+                                    size_t shard_stride, const uint32_t *present_mask,
+                                    const uint32_t *block_len, int32_t *block_status, int flags);
+int fec_rs_recover_ragged_batch(fec_ctx *ctx, int k, int m, size_t max_shard_len, size_t nblocks,
+                                const uint8_t *data, size_t data_block_stride,
+                                const uint8_t *parity, size_t parity_block_stride,
+                                size_t shard_stride, const uint32_t *present_mask,
+                                const uint32_t *block_len,
+                                uint8_t *out, size_t out_block_stride, int out_slots,
+                                int32_t *block_status, int flags);
 
 /* XOR(k, 1) encode: parity = XOR of the k data shards. */
 int fec_xor_encode_batch(fec_ctx *ctx, int k, size_t shard_len, size_t nblocks,
