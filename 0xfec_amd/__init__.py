@@ -80,6 +80,8 @@ lib.fec_rs_encode_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp,
 lib.fec_rs_reconstruct_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
 lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _i, _vp,
                                             _i]
+lib.fec_rs_verify_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
+lib.fec_rs_reconstruct_some_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
 lib.fec_xor_encode_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_xor_reconstruct_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 _u64 = ctypes.c_uint64
@@ -450,6 +452,72 @@ class Codec:
         return _check(self.rs_recover_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
                                                  self._dev(masks), self._lens_addr(lens, B), self._dev(out),
                                                  slots * S, slots, sa), "fec_rs_recover_ragged_batch")
+
+    # ---- verify and reconstruct-some (FEC_DEVICE only; device tensors). Verify: status is an int32
+    # device tensor [B] (1 = the block's parity matches its data, 0 = not), count an optional
+    # uint32 / int32 device tensor of one element that receives the number of bad blocks.
+    # Reconstruct-some: masks and want (optional; None = every shard) are uint32 / int32 device
+    # tensors [B]; missing parity shards are rebuilt too. The raw mirrors return the C return code.
+    def rs_verify_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, status, count=None,
+                      flags=FEC_DEVICE):
+        return lib.fec_rs_verify_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, status, count,
+                                       flags)
+
+    def rs_reconstruct_some_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks, want=None,
+                                status=None, flags=FEC_DEVICE):
+        return lib.fec_rs_reconstruct_some_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                                 masks, want, status, flags)
+
+    @staticmethod
+    def _dev_some(x):
+        a, kind = _addr(x)
+        assert kind == FEC_DEVICE, "verify and reconstruct-some take device memory only"
+        return a
+
+    @classmethod
+    def _words_addr(cls, x, count, what):
+        assert x.numel() == count and x.is_contiguous() and x.element_size() == 4, \
+            "%s is a 4-byte integer device tensor of %d element(s)" % (what, count)
+        return cls._dev_some(x)
+
+    def rs_verify(self, k, m, shards, status, count=None, shard_len=None):
+        B, n, S = _shape3(shards)
+        assert n == k + m
+        a = self._dev_some(shards)
+        L = S if shard_len is None else shard_len
+        ca = self._words_addr(count, 1, "count") if count is not None else None
+        return _check(self.rs_verify_raw(k, m, L, B, a, n * S, a + k * S, n * S, S,
+                                         self._words_addr(status, B, "status"), ca), "fec_rs_verify_batch")
+
+    def rs_verify_split(self, k, m, data, parity, status, count=None, shard_len=None):
+        B, kk, S = _shape3(data)
+        B2, mm, S2 = _shape3(parity)
+        assert (kk, mm, B, S) == (k, m, B2, S2)
+        L = S if shard_len is None else shard_len
+        ca = self._words_addr(count, 1, "count") if count is not None else None
+        return _check(self.rs_verify_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity), m * S, S,
+                                         self._words_addr(status, B, "status"), ca), "fec_rs_verify_batch")
+
+    def rs_reconstruct_some(self, k, m, shards, masks, want=None, status=None, shard_len=None):
+        B, n, S = _shape3(shards)
+        assert n == k + m
+        a = self._dev_some(shards)
+        L = S if shard_len is None else shard_len
+        wa = self._words_addr(want, B, "want") if want is not None else None
+        sa = self._words_addr(status, B, "status") if status is not None else None
+        return _check(self.rs_reconstruct_some_raw(k, m, L, B, a, n * S, a + k * S, n * S, S,
+                                                   self._words_addr(masks, B, "masks"), wa, sa),
+                      "fec_rs_reconstruct_some_batch")
+
+    def rs_reconstruct_some_split(self, k, m, data, parity, masks, want=None, status=None, shard_len=None):
+        B, kk, S = _shape3(data)
+        assert kk == k and tuple(parity.shape) == (B, m, S)
+        L = S if shard_len is None else shard_len
+        wa = self._words_addr(want, B, "want") if want is not None else None
+        sa = self._words_addr(status, B, "status") if status is not None else None
+        return _check(self.rs_reconstruct_some_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity),
+                                                   m * S, S, self._words_addr(masks, B, "masks"), wa, sa),
+                      "fec_rs_reconstruct_some_batch")
 
     # ---- synthetic workload on the device (include/fec_synth.h; same bytes as shard.py)
     def synth_data(self, seed, first_block, nblocks, k, payload_len, data, block_stride, shard_stride):

@@ -23,6 +23,8 @@
 #include "../../include/fec_hip.h"
 #include "fec_kernels.hpp"
 #include "fec_ragged.hpp"
+#include "fec_some.hpp"
+#include "fec_verify.hpp"
 #include "fec_wide.hpp"
 #include "gf256.h"
 #include "rs_matrix.hpp"
@@ -225,17 +227,6 @@ static int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             HIP_TRY(hipMalloc(&c.d_single, st.size() * 4));
             HIP_TRY(hipMemcpy(c.d_single, st.data(), st.size() * 4, hipMemcpyHostToDevice));
         }
-        if (k + m <= FEC_MAX_DECODE_SHARDS) {
-            uint8_t dall[FEC_MAX_DECODE_SHARDS] = {};
-            for (int sidx = 0; sidx < k + m; ++sidx) {
-                unsigned d = 0;
-                for (int t = 0; t < k + m; ++t)
-                    if (t != sidx) d += gf::kTables.log[sidx ^ t];
-                dall[sidx] = (uint8_t)(d % 255u);
-            }
-            HIP_TRY(hipMalloc(&c.d_dall, FEC_MAX_DECODE_SHARDS));
-            HIP_TRY(hipMemcpy(c.d_dall, dall, FEC_MAX_DECODE_SHARDS, hipMemcpyHostToDevice));
-        }
         const std::vector<uint8_t> leaves = dyadic_leaves(c.matrix, k, m);
         if (!leaves.empty() && leaves.size() <= (size_t)m * k) {   // staged like m x k tables
             std::vector<uint32_t> dy((size_t)m * k * 8, 0);
@@ -246,6 +237,19 @@ static int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             HIP_TRY(hipMalloc(&c.d_dytabs, dy.size() * 4));
             HIP_TRY(hipMemcpy(c.d_dytabs, dy.data(), dy.size() * 4, hipMemcpyHostToDevice));
         }
+    }
+    // (for m == 0 too: the sorted-plan kernels stage it whatever the code, and a reconstruct of a
+    // code without parity, where every loss is a failed block, takes them on long shards)
+    if (k + m <= FEC_MAX_DECODE_SHARDS) {
+        uint8_t dall[FEC_MAX_DECODE_SHARDS] = {};
+        for (int sidx = 0; sidx < k + m; ++sidx) {
+            unsigned d = 0;
+            for (int t = 0; t < k + m; ++t)
+                if (t != sidx) d += gf::kTables.log[sidx ^ t];
+            dall[sidx] = (uint8_t)(d % 255u);
+        }
+        HIP_TRY(hipMalloc(&c.d_dall, FEC_MAX_DECODE_SHARDS));
+        HIP_TRY(hipMemcpy(c.d_dall, dall, FEC_MAX_DECODE_SHARDS, hipMemcpyHostToDevice));
     }
     auto res = ctx->codes.emplace(key, std::move(c));
     *out = &res.first->second;
@@ -513,6 +517,92 @@ static int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, 
         a.out_bs = out_bs;
         HIP_TRY(fk::launch_rs_plan_wide(p, ctx->stream));
         HIP_TRY(fk::launch_rs_rebuild_wide(a, ctx->stream));
+    }
+    return FEC_OK;
+}
+
+// Verify (fec_verify.hip): statuses pre-set to 1 and the count to 0 on the stream, then the encode's
+// launches (cut under kMaxItems items, parity rows in passes of 16) with the stored parity folded
+// in: a pass clears the word of a block it finds bad and counts it if no earlier pass had.
+static int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                            const uint8_t* parity, size_t pbs, size_t ss, int32_t* status, uint32_t* count) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 1, nblocks, ctx->stream));
+    if (count) HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
+    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
+    const int k = code->k;
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const size_t nb = std::min(per_launch, nblocks - b0);
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::VerifyArgs a{};
+            a.in = data + b0 * dbs;
+            a.par = parity + b0 * pbs + (size_t)r0 * ss;
+            a.in_bs = dbs;
+            a.par_bs = pbs;
+            a.ss = ss;
+            a.k = (uint32_t)k;
+            a.m = (uint32_t)std::min(16, code->m - r0);
+            a.len = (uint32_t)len;
+            a.cps = cps;
+            a.total = (uint32_t)(nb * cps);
+            a.div_cps = fk::make_fastdiv(cps);
+            a.tabs = code->d_tabs + (size_t)r0 * k * 8;
+            a.status = status + b0;
+            a.count = count;
+            HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
+        }
+    }
+    return FEC_OK;
+}
+
+// Reconstruct-some (fec_some.hip): plan records of the slice in block order, then the tiled rebuild
+// into both regions; cut into launches under kPlanBytes of records and kMaxItems items.
+static int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
+                                      size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                                      const uint32_t* want, int32_t* status, int* err) {
+    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
+    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
+    const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
+    size_t per_launch = std::min<size_t>(kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
+    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
+    const int rc = grow_plans(ctx, per_launch * lay.stride);
+    if (rc) return rc;
+    uint32_t G, C, TK;
+    fk::wide_tile_shape(cps, k, &G, &C, &TK);
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const size_t nb = std::min(per_launch, nblocks - b0);
+        fk::SomePlanArgs p{};
+        p.masks = masks + b0;
+        p.want = want ? want + b0 : nullptr;
+        p.plans = ctx->work->d_plans;
+        p.status = status ? status + b0 : nullptr;
+        p.err = err;
+        p.k = k;
+        p.n = k + m;
+        p.nblocks = (uint32_t)nb;
+        p.lay = lay;
+        fk::SomeReconArgs a{};
+        a.data = data + b0 * dbs;
+        a.parity = parity + b0 * pbs;
+        a.dbs = dbs;
+        a.pbs = pbs;
+        a.ss = (uint32_t)ss;
+        a.plans = ctx->work->d_plans;
+        a.lay = lay;
+        a.k = k;
+        a.len = (uint32_t)len;
+        a.cps = cps;
+        a.nblocks = (uint32_t)nb;
+        a.g = G;
+        a.c = C;
+        a.tk = TK;
+        a.nctiles = (cps + C - 1) / C;
+        a.ntiles = (uint32_t)((nb + G - 1) / G) * a.nctiles;
+        a.div_c = fk::make_fastdiv(C);
+        a.div_nct = fk::make_fastdiv(a.nctiles);
+        HIP_TRY(fk::launch_rs_plan_some(p, ctx->stream));
+        HIP_TRY(fk::launch_rs_rebuild_some(a, ctx->stream));
     }
     return FEC_OK;
 }
@@ -1734,6 +1824,149 @@ int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
     return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
                                       parity, parity_block_stride, shard_stride, present_mask, mask_words,
                                       block_status, ctx->d_err, out, out_block_stride, (uint32_t)out_slots);
+}
+
+// ---------------------------------------------------------------- verify, reconstruct-some
+int fec_rs_verify_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
+                        size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                        size_t shard_stride, int32_t* block_status, uint32_t* mismatch_count, int flags) {
+    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
+    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
+    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
+    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
+    int rc = select_device(ctx);
+    if (rc) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0) return FEC_OK;
+    if (!data || !block_status || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
+    if (m == 0) parity = data;   // never read: no parity slot exists
+    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_words(mismatch_count, block_status))) return rc;
+    return rs_verify_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
+                            shard_stride, block_status, mismatch_count);
+}
+
+int fec_rs_reconstruct_some_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
+                                  size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
+                                  size_t shard_stride, const uint32_t* present_mask, const uint32_t* want_mask,
+                                  int32_t* block_status, int flags) {
+    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (k + m > FEC_MAX_DECODE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
+    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
+    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
+    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
+    int rc = select_device(ctx);
+    if (rc) return rc;
+    Code* code = nullptr;
+    if ((rc = get_code(ctx, k, m, &code))) return rc;
+    if (nblocks == 0) return FEC_OK;
+    if (!data || !present_mask || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
+    if (m == 0) parity = data;   // neither read nor written: no parity slot exists
+    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
+    if ((rc = check_device_words(present_mask, block_status))) return rc;
+    if ((rc = check_device_words(want_mask, nullptr))) return rc;
+    return rs_reconstruct_some_device(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
+                                      parity_block_stride, shard_stride, present_mask, want_mask, block_status,
+                                      ctx->d_err);
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the records some_plan_record
+// builds (fec_some.hpp, the function rs_plan_some_kernel runs) against the systematic matrix. For
+// 64 seeded recoverable masks per code, plus all parity lost and, where m >= k, exactly k present
+// with all of them parity: want = every shard; the inputs are the first k present shards, the
+// outputs every missing shard, ascending, and row r equals M[O[r]] * inverse(rows S of M), parity
+// rows included. Then the same mask with a seeded want mask: the outputs are the wanted missing
+// shards with the rows they had, a want mask naming nothing missing gives an empty record, and a
+// mask with k - 1 present gives too-few exactly when something is to rebuild. 0 on success, else
+// 1000 * (code index + 1) + mask index + 1.
+int fec__selftest_some_plan(void) {
+    static const int shapes[][2] = {{8, 4}, {2, 1}, {20, 10}, {10, 22}, {1, 31}, {31, 1}};
+    uint8_t ex768[768];
+    for (uint32_t i = 0; i < 768; ++i) ex768[i] = fk::wide_exp768(i);
+    const uint8_t* lg = gf::kTables.log;
+    uint64_t seed = 0xD1B54A32D192ED03ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix((int)k, (int)n);
+        if (M.empty()) return 1000 * si;
+        const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
+        const uint32_t all = fk::low_mask(n);
+        // stray bits at and above n are set in both masks throughout: they are ignored
+        const uint32_t stray = ~all;
+        std::vector<uint8_t> rec(lay.stride), rec2(lay.stride);
+        const int cases = 64 + 1 + (m >= k ? 1 : 0);
+        for (int ci = 0; ci < cases; ++ci) {
+            const int fail = 1000 * si + ci + 1;
+            uint32_t pres = all;
+            if (ci == 64) {
+                pres = fk::low_mask(k);                    // all parity lost
+            } else if (ci == 65) {
+                pres = (fk::low_mask(k) << k) & all;       // exactly k present, all of them parity
+            } else {
+                for (uint32_t lose = rnd() % (m + 1); lose > 0;) {
+                    const uint32_t i = rnd() % n;
+                    if ((pres >> i) & 1u) {
+                        pres &= ~(1u << i);
+                        --lose;
+                    }
+                }
+            }
+            std::vector<uint8_t> S, O;
+            for (uint32_t i = 0; i < n && S.size() < k; ++i)
+                if ((pres >> i) & 1u) S.push_back((uint8_t)i);
+            for (uint32_t i = 0; i < n; ++i)
+                if (!((pres >> i) & 1u)) O.push_back((uint8_t)i);
+            std::fill(rec.begin(), rec.end(), 0xEE);
+            if (fk::some_plan_record(rec.data(), lay, pres | stray, 0xFFFFFFFFu, k, n, ex768, lg) != 0) return fail;
+            if (rec[lay.nout_off] != O.size()) return fail;
+            if (O.empty()) continue;
+            if (memcmp(&rec[lay.in_off], S.data(), k) || memcmp(&rec[lay.out_off], O.data(), O.size())) return fail;
+            std::vector<uint8_t> inv((size_t)k * k);
+            for (uint32_t p = 0; p < k; ++p) memcpy(&inv[(size_t)p * k], &M[(size_t)S[p] * k], k);
+            if (!rs::invert((int)k, inv.data())) return fail;
+            for (size_t r = 0; r < O.size(); ++r)
+                for (uint32_t p = 0; p < k; ++p) {
+                    uint8_t c = 0;   // (M[o] * inv)[p]
+                    for (uint32_t t = 0; t < k; ++t) c ^= gf::mul(M[(size_t)O[r] * k + t], inv[(size_t)t * k + p]);
+                    if (rec[lay.coef_off + r * k + p] != c) return fail;
+                }
+            // a want mask: only the wanted missing shards, each with the row it had
+            const uint32_t want = rnd() & all;
+            std::fill(rec2.begin(), rec2.end(), 0xEE);
+            if (fk::some_plan_record(rec2.data(), lay, pres, want | stray, k, n, ex768, lg) != 0) return fail;
+            uint32_t r2 = 0;
+            for (size_t r = 0; r < O.size(); ++r) {
+                if (!((want >> O[r]) & 1u)) continue;
+                if (rec2[lay.out_off + r2] != O[r] ||
+                    memcmp(&rec2[lay.coef_off + r2 * k], &rec[lay.coef_off + r * k], k))
+                    return fail;
+                ++r2;
+            }
+            if (rec2[lay.nout_off] != r2) return fail;
+            if (fk::some_plan_record(rec2.data(), lay, pres, pres | stray, k, n, ex768, lg) != 0 || rec2[lay.nout_off])
+                return fail;
+            // k - 1 present: too few exactly when something is to rebuild
+            uint32_t few = 0;
+            for (uint32_t p = 0; p + 1 < k; ++p) few |= 1u << S[p];
+            if (fk::some_plan_record(rec2.data(), lay, few, 0xFFFFFFFFu, k, n, ex768, lg) != FEC_ERR_TOO_FEW_SHARDS ||
+                rec2[lay.nout_off])
+                return fail;
+            if (fk::some_plan_record(rec2.data(), lay, few, few, k, n, ex768, lg) != 0 || rec2[lay.nout_off]) return fail;
+        }
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------- ragged batches

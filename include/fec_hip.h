@@ -23,6 +23,12 @@
  *                               Encode / ReconstructData / the copy-out for a batch whose blocks
  *                               each have their own shard length, as the reference's blocks do
  *                               (2 + biggestSourceSymbolLenSoFar, reed_solomon.go:47,80)
+ *   fec_rs_verify_batch         Encoder.Verify(shards), batched: one verdict per block (klauspost's
+ *                               interface; the reference does not call it)
+ *   fec_rs_reconstruct_some_batch
+ *                               Encoder.Reconstruct (want_mask NULL) and Encoder.ReconstructSome, in
+ *                               place: missing parity shards are rebuilt too (klauspost's interface;
+ *                               the reference calls ReconstructData only)
  *   fec_xor_encode_batch        xorScheme.xor loop          internal/fec/xor.go:28-33,44-56
  *   fec_xor_reconstruct_batch   xorScheme recover loops     internal/fec/xor.go:80-86
  *
@@ -250,6 +256,56 @@ int fec_rs_recover_ragged_batch(fec_ctx *ctx, int k, int m, size_t max_shard_len
                                 const uint32_t *block_len,
                                 uint8_t *out, size_t out_block_stride, int out_slots,
                                 int32_t *block_status, int flags);
+
+/* RS Verify, batched: block_status[b] = 1 if bytes [0, shard_len) of every parity shard of block b
+ * equal what fec_rs_encode_batch would write there from block b's data shards, else 0. Bytes at and
+ * past shard_len of a slot, data or parity, never influence the result (the tail chunk of a shard
+ * whose length is no multiple of 16 is compared under a byte mask), so the slots may hold anything
+ * there. Nothing but block_status and mismatch_count is written; data and parity are only read.
+ *
+ * Every code the encode takes: k >= 1, m >= 0, k + m <= 256; with m == 0 every status is 1 and the
+ * count 0. block_status (required) is nblocks words of device memory; mismatch_count (optional) is
+ * one device uint32: when the call's work completes on the stream it holds the exact number of
+ * blocks with status 0 (each bad block counted once). The call sets it; the caller need not clear
+ * it. Both are 4-byte aligned (else FEC_ERR_ALIGNMENT). A mismatch is a result, not an error: it
+ * does not touch the sticky word, and fec_sync() returns FEC_OK after it.
+ *
+ * FEC_DEVICE only: any other `flags` value returns FEC_ERR_INVALID_ARG. There is no host-resident
+ * form: it would move k + m shards per block over the host link to learn one bit per block, which a
+ * CPU encoder does faster where the shards already are. Layout and alignment rules are the uniform
+ * calls'; the host-side checks run in their order (shard counts, flags, shard_len, ctx and code,
+ * nblocks == 0 returns FEC_OK and touches nothing, then the pointers, the layouts and the word
+ * alignment). Batches are cut into launches as the encode cuts them. */
+int fec_rs_verify_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                        const uint8_t *data, size_t data_block_stride,
+                        const uint8_t *parity, size_t parity_block_stride,
+                        size_t shard_stride, int32_t *block_status,
+                        uint32_t *mismatch_count, int flags);
+
+/* RS Reconstruct / ReconstructSome, in place: as fec_rs_reconstruct_batch (k + m <=
+ * FEC_MAX_DECODE_SHARDS, one uint32 present mask per block), but missing PARITY shards are rebuilt
+ * as well, and a want mask chooses which missing shards. want_mask is one uint32 per block in
+ * device memory, 4-byte aligned, or NULL for "every shard" (klauspost Reconstruct). Block b rebuilds
+ * the shards  R = ~present_mask[b] & want_mask[b] & low_mask(k + m); bits at and above k + m of
+ * either mask are ignored.
+ *   R empty                              the block is untouched, status 0
+ *   R non-empty, fewer than k present    the block is untouched, status FEC_ERR_TOO_FEW_SHARDS, and
+ *                                        fec_sync() reports it as for the narrow call
+ *   otherwise                            every shard in R, data or parity, is rebuilt into its own
+ *                                        slot from the first k present shards in index order; status 0
+ * A rebuilt shard's slot receives bytes [0, shard_len) and zeros up to round_up(shard_len, 16);
+ * nothing else is written anywhere, missing shards outside R included. Each shard is the value of
+ * one polynomial of degree < k at the shard's index, so a rebuilt parity shard is byte for byte
+ * what fec_rs_encode_batch writes from the block's data. A want mask naming only data shards
+ * (low_mask(k)) gives exactly the bytes and statuses of fec_rs_reconstruct_batch, by a plainer
+ * route than that call's tuned kernels. FEC_DEVICE only (any other `flags` value returns
+ * FEC_ERR_INVALID_ARG); the host-side checks are those of fec_rs_reconstruct_batch, with parity
+ * required when m > 0. */
+int fec_rs_reconstruct_some_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                                  uint8_t *data, size_t data_block_stride,
+                                  uint8_t *parity, size_t parity_block_stride,
+                                  size_t shard_stride, const uint32_t *present_mask,
+                                  const uint32_t *want_mask, int32_t *block_status, int flags);
 
 /* XOR(k, 1) encode: parity = XOR of the k data shards. */
 int fec_xor_encode_batch(fec_ctx *ctx, int k, size_t shard_len, size_t nblocks,
