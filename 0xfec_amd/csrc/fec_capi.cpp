@@ -259,56 +259,38 @@ static int get_code(fec_ctx* ctx, int k, int m, Code** out) {
     return FEC_OK;
 }
 
+// Grow the buffers that share capacity *cap (counted in units of `unit` bytes) to hold n units:
+// pinned host memory where `pinned`, else device memory. The old buffers are freed only after
+// ctx->stream, the only stream that reads them, has drained.
+struct GrowBuf {
+    void** p;
+    bool pinned;
+};
+static int grow(fec_ctx* ctx, size_t* cap, size_t n, size_t unit, std::initializer_list<GrowBuf> bufs) {
+    if (n <= *cap) return FEC_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *cap = 0;
+    for (const GrowBuf& b : bufs) {
+        void* old = *b.p;
+        *b.p = nullptr;
+        if (old) HIP_TRY(b.pinned ? hipHostFree(old) : hipFree(old));
+    }
+    for (const GrowBuf& b : bufs)
+        HIP_TRY(b.pinned ? hipHostMalloc(b.p, n * unit, hipHostMallocDefault) : hipMalloc(b.p, n * unit));
+    *cap = n;
+    return FEC_OK;
+}
 static int grow_plans(fec_ctx* ctx, size_t bytes) {
-    Work& w = *ctx->work;
-    if (bytes <= w.plans_cap) return FEC_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));   // the only stream that reads this workspace
-    if (w.d_plans) HIP_TRY(hipFree(w.d_plans));
-    w.d_plans = nullptr;
-    w.plans_cap = 0;
-    HIP_TRY(hipMalloc(&w.d_plans, bytes));
-    w.plans_cap = bytes;
-    return FEC_OK;
+    return grow(ctx, &ctx->work->plans_cap, bytes, 1, {{(void**)&ctx->work->d_plans, false}});
 }
-
 static int grow_wflags(fec_ctx* ctx, size_t n) {
-    Work& w = *ctx->work;
-    if (n <= w.wflags_cap) return FEC_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (w.d_wflags) HIP_TRY(hipFree(w.d_wflags));
-    w.d_wflags = nullptr;
-    w.wflags_cap = 0;
-    HIP_TRY(hipMalloc(&w.d_wflags, n * 4));
-    w.wflags_cap = n;
-    return FEC_OK;
+    return grow(ctx, &ctx->work->wflags_cap, n, 4, {{(void**)&ctx->work->d_wflags, false}});
 }
-
 static int grow_stage(fec_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->stage_cap) return FEC_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_stage) HIP_TRY(hipHostFree(ctx->h_stage));
-    if (ctx->d_stage) HIP_TRY(hipFree(ctx->d_stage));
-    ctx->h_stage = nullptr;
-    ctx->d_stage = nullptr;
-    ctx->stage_cap = 0;
-    HIP_TRY(hipHostMalloc(&ctx->h_stage, bytes, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&ctx->d_stage, bytes));
-    ctx->stage_cap = bytes;
-    return FEC_OK;
+    return grow(ctx, &ctx->stage_cap, bytes, 1, {{(void**)&ctx->h_stage, true}, {(void**)&ctx->d_stage, false}});
 }
-
 static int grow_masks(fec_ctx* ctx, size_t n) {
-    if (n <= ctx->masks_cap) return FEC_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_masks) HIP_TRY(hipFree(ctx->d_masks));
-    if (ctx->d_status) HIP_TRY(hipFree(ctx->d_status));
-    ctx->d_masks = nullptr;
-    ctx->d_status = nullptr;
-    ctx->masks_cap = 0;
-    HIP_TRY(hipMalloc(&ctx->d_masks, n * 4));
-    HIP_TRY(hipMalloc(&ctx->d_status, n * 4));
-    ctx->masks_cap = n;
-    return FEC_OK;
+    return grow(ctx, &ctx->masks_cap, n, 4, {{(void**)&ctx->d_masks, false}, {(void**)&ctx->d_status, false}});
 }
 
 static size_t round16(size_t x) { return (x + 15) & ~size_t(15); }
@@ -320,39 +302,113 @@ static int flat_grid(uint32_t total) {
 
 // ---------------------------------------------------------------- device-memory cores
 
+// A batch is cut into launches of consecutive blocks: fewer than kMaxItems items (block, chunk)
+// each, and, where a launch keeps a plan record of `stride` bytes per block, at most kPlanBytes of
+// records.
+static uint32_t chunks_of(size_t len) { return (uint32_t)((len + fk::kChunk - 1) / fk::kChunk); }
+
+static size_t blocks_per_launch(size_t nblocks, uint32_t cps, size_t stride = 0) {
+    size_t per = (size_t)(kMaxItems / cps);
+    if (stride) per = std::min(per, kPlanBytes / stride);
+    return std::max<size_t>(1, std::min(per, nblocks));
+}
+
+// body(b0, nb) for each launch's blocks [b0, b0 + nb), until one fails.
+template <class F>
+static int for_slices(size_t nblocks, size_t per_launch, F body) {
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const int rc = body(b0, std::min(per_launch, nblocks - b0));
+        if (rc) return rc;
+    }
+    return FEC_OK;
+}
+
+// What EncodeArgs, VerifyArgs and RagEncodeArgs share: the data of the launch's first block and the
+// tables of the pass of up to 16 parity rows from r0.
+template <class Args>
+static void fill_row_pass(Args& a, const Code* code, int r0, const uint8_t* data, size_t dbs, size_t ss) {
+    a.in = data;
+    a.in_bs = dbs;
+    a.ss = ss;
+    a.k = (uint32_t)code->k;
+    a.m = (uint32_t)std::min(16, code->m - r0);
+    a.tabs = code->d_tabs + (size_t)r0 * code->k * 8;
+}
+
 static int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data,
                             size_t dbs, uint8_t* parity, size_t pbs, size_t ss) {
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
-    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
+    const uint32_t cps = chunks_of(len);
     const int k = code->k;
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
-            const int mr = std::min(16, code->m - r0);
             fk::EncodeArgs a{};
-            a.in = data + b0 * dbs;
+            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
             a.out = parity + b0 * pbs + (size_t)r0 * ss;
-            a.in_bs = dbs;
             a.out_bs = pbs;
-            a.ss = ss;
-            a.k = (uint32_t)k;
-            a.m = (uint32_t)mr;
             a.len = (uint32_t)len;
             a.cps = cps;
             a.total = (uint32_t)(nb * cps);
             a.div_cps = fk::make_fastdiv(cps);
-            a.tabs = code->d_tabs + (size_t)r0 * k * 8;
-            a.dytabs = (r0 == 0 && mr == code->m) ? code->d_dytabs : nullptr;
+            a.dytabs = (r0 == 0 && (int)a.m == code->m) ? code->d_dytabs : nullptr;
             a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {data, dbs, ss, (uint64_t)k},
                                            {parity, pbs, ss, (uint64_t)code->m}, len, nblocks);
-            if (fk::fixed_encode_applies((uint32_t)k, (uint32_t)mr, a.dytabs != nullptr)) {
+            if (fk::fixed_encode_applies((uint32_t)k, a.m, a.dytabs != nullptr)) {
                 HIP_TRY(fk::launch_rs_encode_fixed(a, ctx->stream));
                 continue;
             }
             HIP_TRY(fk::launch_rs_encode(a, flat_grid(a.total), ctx->stream));
         }
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
+}
+
+// What a slice's PlanArgs and ReconArgs hold in the uniform and the ragged reconstruct alike: blocks
+// [b0, b0 + nb) of the call, records of layout `lay` in the stream's workspace, tiles of G blocks.
+struct ReconCall {
+    uint8_t* data;
+    size_t dbs;
+    const uint8_t* parity;
+    size_t pbs, ss, pss;
+    const uint32_t* masks;
+    int32_t* status;
+    int* err;
+    uint8_t* out;
+    size_t out_bs;
+    uint32_t out_slots;
+};
+static void fill_recon_slice(fk::PlanArgs& p, fk::ReconArgs& a, fec_ctx* ctx, const Code* code, const ReconCall& c,
+                             size_t len, uint32_t cps, uint32_t maxe, const fk::PlanLayout& lay, uint32_t G,
+                             size_t b0, size_t nb) {
+    p.masks = c.masks + b0;
+    p.plans = ctx->work->d_plans;
+    p.status = c.status ? c.status + b0 : nullptr;
+    p.err = c.err;
+    p.prows = code->d_prows;
+    p.k = (uint32_t)code->k;
+    p.m = (uint32_t)code->m;
+    p.nblocks = (uint32_t)nb;
+    p.maxe = maxe;
+    p.lay = lay;
+    p.max_out = c.out ? c.out_slots : 0;
+    p.dall = code->d_dall;   // (read by the sorted plans only)
+    a.data = c.data + b0 * c.dbs;
+    a.parity = c.parity + b0 * c.pbs;
+    a.dbs = c.dbs;
+    a.pbs = c.pbs;
+    a.ss = c.ss;
+    a.pss = c.pss;
+    a.plans = ctx->work->d_plans;
+    a.k = p.k;
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.nblocks = (uint32_t)nb;
+    a.maxe = maxe;
+    a.lay = lay;
+    a.g = G;
+    a.ntiles = (uint32_t)((nb + G - 1) / G);
+    a.div_cps = fk::make_fastdiv(cps);
+    a.out = c.out ? c.out + b0 * c.out_bs : nullptr;
+    a.out_bs = c.out_bs;
 }
 
 static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, uint8_t* data,
@@ -363,7 +419,7 @@ static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nb
     if ((ss | pss) >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernels take 32-bit shard strides
     const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
     const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
+    const uint32_t cps = chunks_of(len);
     const fk::PlanLayout lay_block = fk::plan_layout(k, maxe), lay_sorted = fk::plan_layout(k, maxe, true);
     // Three forms:
     //  * direct (fec_recover.hip): no plan kernel; single-erasure tables of the code, for calls
@@ -382,8 +438,7 @@ static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nb
     const bool routed = wave && !out && code->d_single_coef && !fk::rebuild_k_applies(k, maxe, cps) &&
                         fk::routed_recon_applies(k, m, cps, maxe, lay_sorted.stride);
     const fk::PlanLayout lay = wave ? lay_sorted : lay_block;
-    size_t per_launch = std::min<size_t>(direct ? nblocks : kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
-    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
+    const size_t per_launch = blocks_per_launch(nblocks, cps, direct ? 0 : lay.stride);
     if (!direct) {
         const int rc = grow_plans(ctx, per_launch * lay.stride);
         if (rc) return rc;
@@ -393,41 +448,12 @@ static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nb
         if (rc) return rc;
     }
     const uint32_t G = fk::pick_tile_blocks(cps, k, maxe, lay);
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
+    const ReconCall call{data, dbs, parity, pbs, ss, pss, masks, status, err, out, out_bs, out_slots};
+    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
         fk::PlanArgs p{};
-        p.masks = masks + b0;
-        p.plans = ctx->work->d_plans;
-        p.status = status ? status + b0 : nullptr;
-        p.err = err;
-        p.prows = code->d_prows;
-        p.k = k;
-        p.m = m;
-        p.nblocks = (uint32_t)nb;
-        p.maxe = maxe;
-        p.lay = lay;
-        p.max_out = out ? out_slots : 0;
-        p.dall = code->d_dall;
         fk::ReconArgs a{};
-        a.data = data + b0 * dbs;
-        a.parity = parity + b0 * pbs;
-        a.dbs = dbs;
-        a.pbs = pbs;
-        a.ss = ss;
-        a.pss = pss;
-        a.plans = ctx->work->d_plans;
-        a.k = k;
-        a.len = (uint32_t)len;
-        a.cps = cps;
-        a.nblocks = (uint32_t)nb;
-        a.maxe = maxe;
-        a.lay = lay;
-        a.g = G;
-        a.ntiles = (uint32_t)((nb + G - 1) / G);
-        a.div_cps = fk::make_fastdiv(cps);
+        fill_recon_slice(p, a, ctx, code, call, len, cps, maxe, lay, G, b0, nb);
         a.sorted = wave ? 1u : 0u;
-        a.out = out ? out + b0 * out_bs : nullptr;
-        a.out_bs = out_bs;
         if (direct || routed) {
             a.masks = p.masks;
             a.status = p.status;
@@ -456,44 +482,27 @@ static int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nb
             HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
             HIP_TRY(fk::launch_rs_reconstruct(a, (int)std::max<uint32_t>(1, a.ntiles), ctx->stream));
         }
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
 }
 
-// Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
-// up to 256 shards. Plan records of the whole slice, then the tiled rebuild; batches are cut into
-// launches under kPlanBytes of records and kMaxItems items, as above.
-static int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
-                                      size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
-                                      const uint32_t* masks, size_t mask_words, int32_t* status, int* err,
-                                      uint8_t* out = nullptr, size_t out_bs = 0, uint32_t out_slots = 0) {
+// The wide tile (fec_wide.hip rs_rebuild_wide_kernel) over a batch: records of `rows` output rows per
+// block, cut into launches under kPlanBytes of records and kMaxItems items; for each, plan(b0, nb,
+// lay) writes the launch's records into the stream's workspace, then the tile rebuilds from them:
+// `some` false into out (if set) or the data region, true into the data and the parity region.
+template <class Plan>
+static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, size_t len, size_t nblocks, uint8_t* data,
+                            size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, uint8_t* out, size_t out_bs,
+                            bool some, Plan plan) {
     if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
-    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
-    uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
-    if (out) rows = std::min(rows, out_slots);
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
+    const uint32_t cps = chunks_of(len);
     const fk::WideLayout lay = fk::wide_layout(k, rows);
-    size_t per_launch = std::min<size_t>(kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
-    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
+    const size_t per_launch = blocks_per_launch(nblocks, cps, lay.stride);
     const int rc = grow_plans(ctx, per_launch * lay.stride);
     if (rc) return rc;
     uint32_t G, C, TK;
     fk::wide_tile_shape(cps, k, &G, &C, &TK);
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
-        fk::WidePlanArgs p{};
-        p.masks = masks + b0 * mask_words;
-        p.mask_words = (uint32_t)mask_words;
-        p.plans = ctx->work->d_plans;
-        p.status = status ? status + b0 : nullptr;
-        p.err = err;
-        p.k = k;
-        p.n = k + m;
-        p.nblocks = (uint32_t)nb;
-        p.rows = rows;
-        p.max_out = out ? out_slots : 0;
-        p.lay = lay;
-        p.div_k = fk::make_fastdiv(k);
+    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
         fk::WideReconArgs a{};
         a.data = data + b0 * dbs;
         a.parity = parity + b0 * pbs;
@@ -515,10 +524,38 @@ static int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, 
         a.div_nct = fk::make_fastdiv(a.nctiles);
         a.out = out ? out + b0 * out_bs : nullptr;
         a.out_bs = out_bs;
-        HIP_TRY(fk::launch_rs_plan_wide(p, ctx->stream));
-        HIP_TRY(fk::launch_rs_rebuild_wide(a, ctx->stream));
-    }
-    return FEC_OK;
+        HIP_TRY(plan(b0, nb, lay));
+        HIP_TRY(fk::launch_rs_rebuild_wide(a, some, ctx->stream));
+        return FEC_OK;
+    });
+}
+
+// Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
+// up to 256 shards.
+static int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
+                                      size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
+                                      const uint32_t* masks, size_t mask_words, int32_t* status, int* err,
+                                      uint8_t* out = nullptr, size_t out_bs = 0, uint32_t out_slots = 0) {
+    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
+    if (out) rows = std::min(rows, out_slots);
+    return rs_rebuild_tiles(ctx, k, rows, len, nblocks, data, dbs, parity, pbs, ss, out, out_bs, false,
+                            [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                fk::WidePlanArgs p{};
+                                p.masks = masks + b0 * mask_words;
+                                p.mask_words = (uint32_t)mask_words;
+                                p.plans = ctx->work->d_plans;
+                                p.status = status ? status + b0 : nullptr;
+                                p.err = err;
+                                p.k = k;
+                                p.n = k + m;
+                                p.nblocks = (uint32_t)nb;
+                                p.rows = rows;
+                                p.max_out = out ? out_slots : 0;
+                                p.lay = lay;
+                                p.div_k = fk::make_fastdiv(k);
+                                return fk::launch_rs_plan_wide(p, ctx->stream);
+                            });
 }
 
 // Verify (fec_verify.hip): statuses pre-set to 1 and the count to 0 on the stream, then the encode's
@@ -528,83 +565,45 @@ static int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks
                             const uint8_t* parity, size_t pbs, size_t ss, int32_t* status, uint32_t* count) {
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 1, nblocks, ctx->stream));
     if (count) HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
-    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
-    const int k = code->k;
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
             fk::VerifyArgs a{};
-            a.in = data + b0 * dbs;
+            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
             a.par = parity + b0 * pbs + (size_t)r0 * ss;
-            a.in_bs = dbs;
             a.par_bs = pbs;
-            a.ss = ss;
-            a.k = (uint32_t)k;
-            a.m = (uint32_t)std::min(16, code->m - r0);
             a.len = (uint32_t)len;
             a.cps = cps;
             a.total = (uint32_t)(nb * cps);
             a.div_cps = fk::make_fastdiv(cps);
-            a.tabs = code->d_tabs + (size_t)r0 * k * 8;
             a.status = status + b0;
             a.count = count;
             HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
         }
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
 }
 
-// Reconstruct-some (fec_some.hip): plan records of the slice in block order, then the tiled rebuild
-// into both regions; cut into launches under kPlanBytes of records and kMaxItems items.
+// Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
+// the wide tile, storing into both regions.
 static int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
                                       size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
                                       const uint32_t* want, int32_t* status, int* err) {
-    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
-    const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
-    size_t per_launch = std::min<size_t>(kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
-    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
-    const int rc = grow_plans(ctx, per_launch * lay.stride);
-    if (rc) return rc;
-    uint32_t G, C, TK;
-    fk::wide_tile_shape(cps, k, &G, &C, &TK);
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
-        fk::SomePlanArgs p{};
-        p.masks = masks + b0;
-        p.want = want ? want + b0 : nullptr;
-        p.plans = ctx->work->d_plans;
-        p.status = status ? status + b0 : nullptr;
-        p.err = err;
-        p.k = k;
-        p.n = k + m;
-        p.nblocks = (uint32_t)nb;
-        p.lay = lay;
-        fk::SomeReconArgs a{};
-        a.data = data + b0 * dbs;
-        a.parity = parity + b0 * pbs;
-        a.dbs = dbs;
-        a.pbs = pbs;
-        a.ss = (uint32_t)ss;
-        a.plans = ctx->work->d_plans;
-        a.lay = lay;
-        a.k = k;
-        a.len = (uint32_t)len;
-        a.cps = cps;
-        a.nblocks = (uint32_t)nb;
-        a.g = G;
-        a.c = C;
-        a.tk = TK;
-        a.nctiles = (cps + C - 1) / C;
-        a.ntiles = (uint32_t)((nb + G - 1) / G) * a.nctiles;
-        a.div_c = fk::make_fastdiv(C);
-        a.div_nct = fk::make_fastdiv(a.nctiles);
-        HIP_TRY(fk::launch_rs_plan_some(p, ctx->stream));
-        HIP_TRY(fk::launch_rs_rebuild_some(a, ctx->stream));
-    }
-    return FEC_OK;
+    return rs_rebuild_tiles(ctx, k, fk::some_rows(m), len, nblocks, data, dbs, parity, pbs, ss, nullptr, 0, true,
+                            [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                fk::SomePlanArgs p{};
+                                p.masks = masks + b0;
+                                p.want = want ? want + b0 : nullptr;
+                                p.plans = ctx->work->d_plans;
+                                p.status = status ? status + b0 : nullptr;
+                                p.err = err;
+                                p.k = k;
+                                p.n = k + m;
+                                p.nblocks = (uint32_t)nb;
+                                p.lay = lay;
+                                return fk::launch_rs_plan_some(p, ctx->stream);
+                            });
 }
 
 // Ragged batches (fec_ragged.hip): block b's shards are lens[b] bytes long, at most max_len. Cut
@@ -619,22 +618,14 @@ static uint32_t ragged_encode_blocks(uint32_t cps_max) {
 static int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, const uint8_t* data,
                                    size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* lens,
                                    int32_t* status, int* err) {
-    const uint32_t cps = (uint32_t)((max_len + fk::kChunk - 1) / fk::kChunk);
-    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
-    const int k = code->k;
+    const uint32_t cps = chunks_of(max_len);
     const uint32_t G = ragged_encode_blocks(cps);
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
-            const int mr = std::min(16, code->m - r0);
             fk::RagEncodeArgs a{};
-            a.in = data + b0 * dbs;
+            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
             a.out = parity + b0 * pbs + (size_t)r0 * ss;
-            a.in_bs = dbs;
             a.out_bs = pbs;
-            a.ss = ss;
-            a.k = (uint32_t)k;
-            a.m = (uint32_t)mr;
             a.max_len = (uint32_t)max_len;
             a.nblocks = (uint32_t)nb;
             a.g = G;
@@ -643,11 +634,10 @@ static int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, siz
             a.status = status ? status + b0 : nullptr;
             a.err = err;
             a.report = r0 == 0;
-            a.tabs = code->d_tabs + (size_t)r0 * k * 8;
             HIP_TRY(fk::launch_rs_encode_ragged(a, ctx->stream));
         }
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
 }
 
 // Plans in block order by rs_plan_kernel (they do not depend on the length), then the ragged tile
@@ -659,10 +649,9 @@ static int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len
     if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild takes 32-bit shard strides
     const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
     const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
-    const uint32_t cps = (uint32_t)((max_len + fk::kChunk - 1) / fk::kChunk);
+    const uint32_t cps = chunks_of(max_len);
     const fk::PlanLayout lay = fk::plan_layout(k, maxe);
-    size_t per_launch = std::min<size_t>(kPlanBytes / lay.stride, (size_t)(kMaxItems / cps));
-    per_launch = std::max<size_t>(1, std::min(per_launch, nblocks));
+    const size_t per_launch = blocks_per_launch(nblocks, cps, lay.stride);
     const int rc = grow_plans(ctx, per_launch * lay.stride);
     if (rc) return rc;
     // rows a block can need: the plan kernel gives a block with more erasures than slots no rows
@@ -676,108 +665,73 @@ static int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len
     const int forced = fk::g_tune.rag_g;
     uint32_t G = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps);
     G = fk::rag_clamp_blocks(std::min(G, fk::rag_recon_max_blocks(k, rows, lay)), cps);
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
+    const ReconCall call{data, dbs, parity, pbs, ss, ss, masks, status, err, out, out_bs, out_slots};
+    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
         fk::PlanArgs p{};
-        p.masks = masks + b0;
-        p.plans = ctx->work->d_plans;
-        p.status = status ? status + b0 : nullptr;
-        p.err = err;
-        p.prows = code->d_prows;
-        p.k = k;
-        p.m = m;
-        p.nblocks = (uint32_t)nb;
-        p.maxe = maxe;
-        p.lay = lay;
-        p.max_out = out ? out_slots : 0;
         fk::RagReconArgs ra{};
-        fk::ReconArgs& a = ra.r;
-        a.data = data + b0 * dbs;
-        a.parity = parity + b0 * pbs;
-        a.dbs = dbs;
-        a.pbs = pbs;
-        a.ss = ss;
-        a.pss = ss;
-        a.plans = ctx->work->d_plans;
-        a.k = k;
-        a.len = (uint32_t)max_len;
-        a.cps = cps;
-        a.nblocks = (uint32_t)nb;
-        a.maxe = maxe;
-        a.lay = lay;
-        a.g = G;
-        a.ntiles = (uint32_t)((nb + G - 1) / G);
-        a.div_cps = fk::make_fastdiv(cps);
-        a.out = out ? out + b0 * out_bs : nullptr;
-        a.out_bs = out_bs;
-        a.status = p.status;
-        a.err = err;
+        fill_recon_slice(p, ra.r, ctx, code, call, max_len, cps, maxe, lay, G, b0, nb);
+        ra.r.status = p.status;
+        ra.r.err = err;
         ra.lens = lens + b0;
         ra.max_len = (uint32_t)max_len;
         ra.nwin = fk::rag_windows(G, cps);
         ra.rows = rows;
         HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
         HIP_TRY(fk::launch_rs_reconstruct_ragged(ra, ctx->stream));
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
+}
+
+// The XOR calls' launch arguments for blocks [b0, b0 + nb): the encode's, and the in-place
+// reconstruct's (data rebuilt where it lies, parity read).
+static fk::XorArgs xor_slice(int k, size_t len, uint32_t cps, const uint8_t* in, size_t in_bs, uint8_t* out,
+                             size_t out_bs, size_t ss, size_t b0, size_t nb) {
+    fk::XorArgs a{};
+    a.in = in + b0 * in_bs;
+    a.out = out + b0 * out_bs;
+    a.in_bs = in_bs;
+    a.out_bs = out_bs;
+    a.ss = ss;
+    a.k = (uint32_t)k;
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.total = (uint32_t)(nb * cps);
+    a.div_cps = fk::make_fastdiv(cps);
+    return a;
 }
 
 static int xor_encode_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
                              uint8_t* parity, size_t pbs, size_t ss) {
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
-    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
-        fk::XorArgs a{};
-        a.in = data + b0 * dbs;
-        a.out = parity + b0 * pbs;
-        a.in_bs = dbs;
-        a.out_bs = pbs;
-        a.ss = ss;
-        a.k = (uint32_t)k;
-        a.len = (uint32_t)len;
-        a.cps = cps;
-        a.total = (uint32_t)(nb * cps);
-        a.div_cps = fk::make_fastdiv(cps);
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        const fk::XorArgs a = xor_slice(k, len, cps, data, dbs, parity, pbs, ss, b0, nb);
         HIP_TRY(fk::launch_xor_encode(a, flat_grid(a.total), ctx->stream));
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
 }
 
 static int xor_reconstruct_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
                                   const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
                                   int32_t* status, int* err) {
-    const uint32_t cps = (uint32_t)((len + fk::kChunk - 1) / fk::kChunk);
-    const size_t per_launch = std::max<size_t>(1, (size_t)(kMaxItems / cps));
-    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-        const size_t nb = std::min(per_launch, nblocks - b0);
-        fk::XorArgs a{};
-        a.in = data + b0 * dbs;
-        a.out = data + b0 * dbs;
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        fk::XorArgs a = xor_slice(k, len, cps, data, dbs, data, dbs, ss, b0, nb);
         a.parity = parity + b0 * pbs;
-        a.in_bs = dbs;
-        a.out_bs = dbs;
         a.par_bs = pbs;
-        a.ss = ss;
         a.masks = masks + b0;
         a.status = status ? status + b0 : nullptr;
         a.err = err;
-        a.k = (uint32_t)k;
-        a.len = (uint32_t)len;
-        a.cps = cps;
-        a.total = (uint32_t)(nb * cps);
         a.nblocks = (uint32_t)nb;
-        a.div_cps = fk::make_fastdiv(cps);
         HIP_TRY(fk::launch_xor_reconstruct(a, flat_grid(a.total), ctx->stream));
-    }
-    return FEC_OK;
+        return FEC_OK;
+    });
 }
 
 // ---------------------------------------------------------------- validation helpers
 
 // FEC_DEVICE masks and statuses are read and written as 4-byte words (the masks by scalar loads,
 // which ignore the low two address bits: a misaligned mask array would be read wrong, silently).
-static int check_device_words(const uint32_t* masks, const int32_t* status) {
+static int check_device_words(const void* masks, const void* status) {
     return (((uintptr_t)masks | (uintptr_t)status) & 3u) ? FEC_ERR_ALIGNMENT : FEC_OK;
 }
 
@@ -1687,26 +1641,70 @@ int fec_rs_prepare(fec_ctx* ctx, int k, int m) {
     return get_code(ctx, k, m, &code);
 }
 
+// The argument checks every batch call makes before it runs, in the documented order (fec_hip.h):
+// shard counts, flags, shard_len, out_slots and mask_words; then the ctx and the code; an empty
+// call; null pointers; and for FEC_DEVICE the layout of the data, parity and out regions, in that
+// order, then the alignment of the word arrays. An entry point describes itself in a Call and gets
+// kRun back when it has work to do, else the code to return.
+struct Call {
+    int k, m, max_n;           // max_n: the call's largest k + m (the XOR calls: m = 1)
+    bool host_ok;              // FEC_HOST / FEC_HOST_PINNED accepted
+    int flags;
+    size_t len, nblocks;
+    const uint8_t* data;
+    size_t dbs;
+    const uint8_t** parity;    // m == 0: set to data (never read: no parity slot exists)
+    size_t pbs, ss;
+    bool rs = true;            // the code's tables are needed (not for XOR)
+    bool encode = false;       // m == 0 leaves nothing to do
+    bool null_arg = false;     // some further pointer the call needs is null
+    bool has_out = false;      // recover calls: the out region and its slot count
+    const uint8_t* out = nullptr;
+    size_t obs = 0;
+    int out_slots = 1;
+    bool wide = false;         // wide calls: words per present mask
+    size_t mask_words = 1;
+    struct {
+        const void *a, *b;
+    } words[2] = {};           // (mask, status)-like pairs of 4-byte arrays, either may be null
+};
+constexpr int kRun = 1;
+
+static int check_call(fec_ctx* ctx, const Call& c, Code** code) {
+    if (c.k <= 0 || c.m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (c.k + c.m > c.max_n) return FEC_ERR_MAX_SHARD_NUM;
+    if (c.flags != FEC_DEVICE && !(c.host_ok && (c.flags == FEC_HOST || c.flags == FEC_HOST_PINNED)))
+        return FEC_ERR_INVALID_ARG;
+    if (c.len == 0) return FEC_ERR_SHARD_NO_DATA;
+    if (c.len > (size_t(1) << 30) || c.out_slots <= 0) return FEC_ERR_INVALID_ARG;
+    if (c.wide && (c.mask_words < (size_t)FEC_MASK_WORDS(c.k + c.m) || c.mask_words > 8)) return FEC_ERR_INVALID_ARG;
+    int rc = select_device(ctx);
+    if (rc) return rc;
+    if (c.rs && (rc = get_code(ctx, c.k, c.m, code))) return rc;
+    if (c.nblocks == 0 || (c.encode && c.m == 0)) return FEC_OK;
+    if (!c.data || c.null_arg || (c.m > 0 && !*c.parity)) return FEC_ERR_INVALID_ARG;
+    if (c.m == 0) *c.parity = c.data;
+    if (c.flags != FEC_DEVICE) return kRun;
+    if ((rc = check_device_layout(c.data, c.dbs, c.ss, c.len))) return rc;
+    if ((rc = check_device_layout(*c.parity, c.pbs, c.ss, c.len))) return rc;
+    if (c.has_out && (rc = check_device_layout(c.out, c.obs, c.ss, c.len))) return rc;
+    for (const auto& w : c.words)
+        if ((rc = check_device_words(w.a, w.b))) return rc;
+    return kRun;
+}
+
 int fec_rs_encode_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
                         size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                         size_t shard_stride, int flags) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE && flags != FEC_HOST && flags != FEC_HOST_PINNED) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
+    const uint8_t* par = parity;
+    Call c{k, m, 256, true, flags, shard_len, nblocks, data, data_block_stride, &par, parity_block_stride, shard_stride};
+    c.encode = true;
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0 || m == 0) return FEC_OK;
-    if (!data || !parity) return FEC_ERR_INVALID_ARG;
-    if (flags == FEC_DEVICE) {
-        if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    if (flags == FEC_DEVICE)
         return rs_encode_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity,
                                 parity_block_stride, shard_stride);
-    }
     return host_encode(ctx, code, k, m, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
                        shard_stride, flags == FEC_HOST_PINNED);
 }
@@ -1714,25 +1712,16 @@ int fec_rs_encode_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nbl
 int fec_rs_reconstruct_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
                              size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                              size_t shard_stride, const uint32_t* present_mask, int32_t* block_status, int flags) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > FEC_MAX_DECODE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE && flags != FEC_HOST && flags != FEC_HOST_PINNED) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, true, flags, shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask;
+    c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;   // never read: no parity slot exists
-    if (flags == FEC_DEVICE) {
-        if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_words(present_mask, block_status))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    if (flags == FEC_DEVICE)
         return rs_reconstruct_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity,
                                      parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err);
-    }
     return host_reconstruct_rs(ctx, code, k, m, shard_len, nblocks, data, data_block_stride, parity,
                                parity_block_stride, shard_stride, present_mask, block_status, flags == FEC_HOST_PINNED);
 }
@@ -1741,61 +1730,40 @@ int fec_rs_recover_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nb
                          size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                          size_t shard_stride, const uint32_t* present_mask, uint8_t* out, size_t out_block_stride,
                          int out_slots, int32_t* block_status, int flags) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > FEC_MAX_DECODE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30) || out_slots <= 0) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask || !out;
+    c.has_out = true, c.out = out, c.obs = out_block_stride, c.out_slots = out_slots;
+    c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || !out || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_layout(out, out_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_words(present_mask, block_status))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
     return rs_reconstruct_device(ctx, code, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
                                  parity, parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err,
                                  out, out_block_stride, (uint32_t)out_slots);
 }
 
-// Argument checks of the wide calls that need no device, in the narrow calls' order.
-static int check_wide_args(int k, int m, size_t shard_len, size_t mask_words, int flags, bool host_ok) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > FEC_MAX_WIDE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE && !(host_ok && (flags == FEC_HOST || flags == FEC_HOST_PINNED))) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    if (mask_words < (size_t)FEC_MASK_WORDS(k + m) || mask_words > 8) return FEC_ERR_INVALID_ARG;
-    return FEC_OK;
-}
-
+// The wide calls with one mask word and a narrow code are the narrow calls, bytes and errors
+// unchanged (which make the same checks: one word is enough for k + m <= 32).
 int fec_rs_reconstruct_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
                                   size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                                   size_t shard_stride, const uint32_t* present_mask, size_t mask_words,
                                   int32_t* block_status, int flags) {
-    int rc = check_wide_args(k, m, shard_len, mask_words, flags, true);
-    if (rc) return rc;
-    if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)   // the narrow call, bytes and errors unchanged
+    if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)
         return fec_rs_reconstruct_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
                                         parity_block_stride, shard_stride, present_mask, block_status, flags);
-    if ((rc = select_device(ctx))) return rc;
+    Call c{k, m, FEC_MAX_WIDE_SHARDS, true, flags, shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask;
+    c.wide = true, c.mask_words = mask_words;
+    c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;   // never read: no parity slot exists
-    if (flags == FEC_DEVICE) {
-        if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_words(present_mask, block_status))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    if (flags == FEC_DEVICE)
         return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
                                           parity_block_stride, shard_stride, present_mask, mask_words, block_status,
                                           ctx->d_err);
-    }
     return host_reconstruct_wide(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
                                  shard_stride, present_mask, mask_words, block_status);
 }
@@ -1804,23 +1772,19 @@ int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
                               size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                               size_t shard_stride, const uint32_t* present_mask, size_t mask_words, uint8_t* out,
                               size_t out_block_stride, int out_slots, int32_t* block_status, int flags) {
-    int rc = check_wide_args(k, m, shard_len, mask_words, flags, false);
-    if (rc) return rc;
-    if (out_slots <= 0) return FEC_ERR_INVALID_ARG;
     if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)
         return fec_rs_recover_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
                                     parity_block_stride, shard_stride, present_mask, out, out_block_stride, out_slots,
                                     block_status, flags);
-    if ((rc = select_device(ctx))) return rc;
+    Call c{k, m, FEC_MAX_WIDE_SHARDS, false, flags, shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask || !out;
+    c.has_out = true, c.out = out, c.obs = out_block_stride, c.out_slots = out_slots;
+    c.wide = true, c.mask_words = mask_words;
+    c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || !out || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_layout(out, out_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_words(present_mask, block_status))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
     return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
                                       parity, parity_block_stride, shard_stride, present_mask, mask_words,
                                       block_status, ctx->d_err, out, out_block_stride, (uint32_t)out_slots);
@@ -1830,21 +1794,13 @@ int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
 int fec_rs_verify_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
                         size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                         size_t shard_stride, int32_t* block_status, uint32_t* mismatch_count, int flags) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
+    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &parity, parity_block_stride,
+           shard_stride};
+    c.null_arg = !block_status;
+    c.words[0] = {mismatch_count, block_status};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !block_status || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;   // never read: no parity slot exists
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_words(mismatch_count, block_status))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
     return rs_verify_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
                             shard_stride, block_status, mismatch_count);
 }
@@ -1853,25 +1809,18 @@ int fec_rs_reconstruct_some_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
                                   size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                                   size_t shard_stride, const uint32_t* present_mask, const uint32_t* want_mask,
                                   int32_t* block_status, int flags) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > FEC_MAX_DECODE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
+    const uint8_t* par = parity;   // (m == 0: neither read nor written)
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, shard_len, nblocks, data, data_block_stride, &par,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask;
+    c.words[0] = {present_mask, block_status};
+    c.words[1] = {want_mask, nullptr};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;   // neither read nor written: no parity slot exists
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-    if ((rc = check_device_words(present_mask, block_status))) return rc;
-    if ((rc = check_device_words(want_mask, nullptr))) return rc;
-    return rs_reconstruct_some_device(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
-                                      parity_block_stride, shard_stride, present_mask, want_mask, block_status,
-                                      ctx->d_err);
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_reconstruct_some_device(ctx, k, m, shard_len, nblocks, data, data_block_stride,
+                                      const_cast<uint8_t*>(par), parity_block_stride, shard_stride, present_mask,
+                                      want_mask, block_status, ctx->d_err);
 }
 
 // Internal self-test (not part of the public ABI, no device needed): the records some_plan_record
@@ -1970,29 +1919,19 @@ int fec__selftest_some_plan(void) {
 }
 
 // ---------------------------------------------------------------- ragged batches
-// Host-side checks in the uniform calls' order, max_shard_len in place of shard_len.
-static int check_ragged_args(int k, int m, int max_n, size_t max_shard_len, int flags) {
-    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + m > max_n) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE) return FEC_ERR_INVALID_ARG;
-    if (max_shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (max_shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    return FEC_OK;
-}
-
+// The uniform calls' checks, max_shard_len in place of shard_len.
 int fec_rs_encode_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, const uint8_t* data,
                                size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                                size_t shard_stride, const uint32_t* block_len, int32_t* block_status, int flags) {
-    int rc = check_ragged_args(k, m, 256, max_shard_len, flags);
-    if (rc) return rc;
-    if ((rc = select_device(ctx))) return rc;
+    const uint8_t* par = parity;
+    Call c{k, m, 256, false, flags, max_shard_len, nblocks, data, data_block_stride, &par, parity_block_stride,
+           shard_stride};
+    c.encode = true;
+    c.null_arg = !block_len;
+    c.words[0] = {block_len, block_status};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0 || m == 0) return FEC_OK;
-    if (!data || !parity || !block_len) return FEC_ERR_INVALID_ARG;
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_words(block_len, block_status))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
     return rs_encode_ragged_device(ctx, code, max_shard_len, nblocks, data, data_block_stride, parity,
                                    parity_block_stride, shard_stride, block_len, block_status, ctx->d_err);
 }
@@ -2001,18 +1940,14 @@ int fec_rs_reconstruct_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard
                                     size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                                     size_t shard_stride, const uint32_t* present_mask, const uint32_t* block_len,
                                     int32_t* block_status, int flags) {
-    int rc = check_ragged_args(k, m, FEC_MAX_DECODE_SHARDS, max_shard_len, flags);
-    if (rc) return rc;
-    if ((rc = select_device(ctx))) return rc;
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, max_shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask || !block_len;
+    c.words[0] = {present_mask, block_status};
+    c.words[1] = {block_len, nullptr};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || !block_len || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;   // never read: no parity slot exists
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_words(present_mask, block_status))) return rc;
-    if ((rc = check_device_words(block_len, nullptr))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
     return rs_reconstruct_ragged_device(ctx, code, max_shard_len, nblocks, data, data_block_stride, parity,
                                         parity_block_stride, shard_stride, present_mask, block_len, block_status,
                                         ctx->d_err);
@@ -2023,20 +1958,15 @@ int fec_rs_recover_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len
                                 size_t shard_stride, const uint32_t* present_mask, const uint32_t* block_len,
                                 uint8_t* out, size_t out_block_stride, int out_slots, int32_t* block_status,
                                 int flags) {
-    int rc = check_ragged_args(k, m, FEC_MAX_DECODE_SHARDS, max_shard_len, flags);
-    if (rc) return rc;
-    if (out_slots <= 0) return FEC_ERR_INVALID_ARG;
-    if ((rc = select_device(ctx))) return rc;
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, max_shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.null_arg = !present_mask || !block_len || !out;
+    c.has_out = true, c.out = out, c.obs = out_block_stride, c.out_slots = out_slots;
+    c.words[0] = {present_mask, block_status};
+    c.words[1] = {block_len, nullptr};
     Code* code = nullptr;
-    if ((rc = get_code(ctx, k, m, &code))) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !present_mask || !block_len || !out || (m > 0 && !parity)) return FEC_ERR_INVALID_ARG;
-    if (m == 0) parity = data;
-    if ((rc = check_device_layout(data, data_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_layout(out, out_block_stride, shard_stride, max_shard_len))) return rc;
-    if ((rc = check_device_words(present_mask, block_status))) return rc;
-    if ((rc = check_device_words(block_len, nullptr))) return rc;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
     return rs_reconstruct_ragged_device(ctx, code, max_shard_len, nblocks, const_cast<uint8_t*>(data),
                                         data_block_stride, parity, parity_block_stride, shard_stride, present_mask,
                                         block_len, block_status, ctx->d_err, out, out_block_stride,
@@ -2182,21 +2112,14 @@ int fec__selftest_wide_plan(void) {
 int fec_xor_encode_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, const uint8_t* data,
                          size_t data_block_stride, uint8_t* parity, size_t parity_block_stride, size_t shard_stride,
                          int flags) {
-    if (k <= 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + 1 > 256) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE && flags != FEC_HOST && flags != FEC_HOST_PINNED) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !parity) return FEC_ERR_INVALID_ARG;
-    if (flags == FEC_DEVICE) {
-        if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
+    const uint8_t* par = parity;
+    Call c{k, 1, 256, true, flags, shard_len, nblocks, data, data_block_stride, &par, parity_block_stride, shard_stride};
+    c.rs = false;
+    const int rc = check_call(ctx, c, nullptr);
+    if (rc != kRun) return rc;
+    if (flags == FEC_DEVICE)
         return xor_encode_device(ctx, k, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
                                  shard_stride);
-    }
     return host_encode(ctx, nullptr, k, 1, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
                        shard_stride, flags == FEC_HOST_PINNED);
 }
@@ -2204,22 +2127,16 @@ int fec_xor_encode_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, 
 int fec_xor_reconstruct_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, uint8_t* data,
                               size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                               size_t shard_stride, const uint32_t* present_mask, int32_t* block_status, int flags) {
-    if (k <= 0) return FEC_ERR_INV_SHARD_NUM;
-    if (k + 1 > FEC_MAX_DECODE_SHARDS) return FEC_ERR_MAX_SHARD_NUM;
-    if (flags != FEC_DEVICE && flags != FEC_HOST && flags != FEC_HOST_PINNED) return FEC_ERR_INVALID_ARG;
-    if (shard_len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (shard_len > (size_t(1) << 30)) return FEC_ERR_INVALID_ARG;
-    int rc = select_device(ctx);
-    if (rc) return rc;
-    if (nblocks == 0) return FEC_OK;
-    if (!data || !parity || !present_mask) return FEC_ERR_INVALID_ARG;
-    if (flags == FEC_DEVICE) {
-        if ((rc = check_device_layout(data, data_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_layout(parity, parity_block_stride, shard_stride, shard_len))) return rc;
-        if ((rc = check_device_words(present_mask, block_status))) return rc;
+    Call c{k, 1, FEC_MAX_DECODE_SHARDS, true, flags, shard_len, nblocks, data, data_block_stride, &parity,
+           parity_block_stride, shard_stride};
+    c.rs = false;
+    c.null_arg = !present_mask;
+    c.words[0] = {present_mask, block_status};
+    const int rc = check_call(ctx, c, nullptr);
+    if (rc != kRun) return rc;
+    if (flags == FEC_DEVICE)
         return xor_reconstruct_device(ctx, k, shard_len, nblocks, data, data_block_stride, parity,
                                       parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err);
-    }
     return host_reconstruct_xor(ctx, k, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
                                 shard_stride, present_mask, block_status);
 }

@@ -162,6 +162,57 @@ __device__ __forceinline__ void split4(Idx (&ix)[4], const uint4& x) {
     ix[3] = split(x.w);
 }
 
+// The generic fold of one group of kInGroup loaded inputs x (inputs j0 .. of `bound`) into the
+// first `rows` (wave-uniform) of ROWS accumulators: inputs in pairs (mac2), an odd last one alone
+// (mac1). Row r's PermTab of input j is T[r * tstride + j].
+template <int ROWS>
+__device__ __forceinline__ void fold_group(uint32_t (&acc)[ROWS][4], const uint4 (&x)[kInGroup], uint32_t rows,
+                                           const gf::PermTab* T, uint32_t tstride, uint32_t j0, uint32_t bound) {
+#pragma unroll
+    for (int jj = 0; jj < kInGroup; jj += 2) {
+        const uint32_t j = j0 + jj;
+        if (j + 1 < bound) {
+            Idx ia[4], ib[4];
+            split4(ia, x[jj]);
+            split4(ib, x[jj + 1]);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r)
+                if (r < (int)rows) mac2(acc[r], ia, ib, T + r * tstride + j, T + r * tstride + j + 1);
+        } else if (j < bound) {
+            Idx ia[4];
+            split4(ia, x[jj]);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r)
+                if (r < (int)rows) mac1(acc[r], ia, T + r * tstride + j);
+        }
+    }
+}
+
+// One group of inputs of a 16-byte chunk column of k shards `ss` apart from src: shards j0 .. j0 + 7,
+// zeros past shard k - 1, by non-temporal loads (+2-5 %). The generic encode's inner
+// loop is  for (j0 = 0; j0 < k; j0 += kInGroup) { load_shards; fold_group }  in each kernel's own
+// body: with the loop itself in a helper the compiler keeps a second group's loads in flight (+28 to
+// 32 VGPRs at 8 rows, 126 -> 154 in rs_encode_kernel<8, false>: one wave per SIMD fewer).
+__device__ __forceinline__ void load_shards(uint4 (&x)[kInGroup], const uint8_t* src, uint64_t ss, uint32_t j0,
+                                            uint32_t k) {
+#pragma unroll
+    for (int jj = 0; jj < kInGroup; ++jj)   // uniform predicate: no loads past shard k-1
+        x[jj] = j0 + jj < k ? ld16<true>(src + (uint64_t)(j0 + jj) * ss) : make_uint4(0, 0, 0, 0);
+}
+
+// The nw table words of a launch: staged into LDS at `lds` by the whole workgroup (the caller's
+// next barrier publishes them), or read where they are in global memory.
+template <bool LDS_TABS>
+__device__ __forceinline__ const gf::PermTab* stage_tabs(const uint32_t* gtabs, uint32_t nw, uint8_t* lds) {
+    if constexpr (LDS_TABS) {
+        uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
+        for (uint32_t i = threadIdx.x; i < nw; i += kThreads) dst[i] = gtabs[i];
+        return reinterpret_cast<const gf::PermTab*>(lds);
+    } else {
+        return reinterpret_cast<const gf::PermTab*>(gtabs);
+    }
+}
+
 // err |= bit from the lanes that reach this point together, as one atomic per wave: the library
 // is built without the compiler's atomic combining (_build.py), and per-lane atomics on one
 // address serialise at L2 (XOR(2,1) with U{1..2} losses, half the blocks failing: 5.97 ms with an

@@ -96,19 +96,11 @@ __device__ __forceinline__ TileSum tile_prefix(const uint32_t* lens, const RagTi
 // before the lengths are read and is published by the prefix's barriers.
 template <int MAXM, bool LDS_TABS>
 __global__ __launch_bounds__(kThreads) void rs_encode_ragged_kernel(RagEncodeArgs a) {
-    constexpr bool NTL = true, NTS = true;
+    constexpr bool NTS = true;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const RagLds L = rag_lds(smem);
     const RagTile T = rag_tile(xcd_order(), a.g, a.nwin, a.nblocks);
-    const gf::PermTab* tabs;
-    if constexpr (LDS_TABS) {
-        uint32_t* dst = reinterpret_cast<uint32_t*>(smem + kRagLds);
-        const uint32_t nw = a.m * a.k * 8;
-        for (uint32_t i = threadIdx.x; i < nw; i += kThreads) dst[i] = a.tabs[i];
-        tabs = reinterpret_cast<const gf::PermTab*>(smem + kRagLds);
-    } else {
-        tabs = reinterpret_cast<const gf::PermTab*>(a.tabs);
-    }
+    const gf::PermTab* tabs = stage_tabs<LDS_TABS>(a.tabs, a.m * a.k * 8, smem + kRagLds);
     const uint32_t total = tile_prefix(a.lens, T, a.max_len, a.status, a.err, a.report && T.win == 0, true, L).total;
     const RagSpan span = rag_span(T.win, total);
     if (span.lo >= span.hi) return;   // workgroup-uniform
@@ -125,27 +117,8 @@ __global__ __launch_bounds__(kThreads) void rs_encode_ragged_kernel(RagEncodeArg
         for (int r = 0; r < MAXM; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0;
         for (uint32_t j0 = 0; j0 < k; j0 += kInGroup) {
             uint4 x[kInGroup];
-#pragma unroll
-            for (int jj = 0; jj < kInGroup; ++jj)   // uniform predicate: no loads past shard k-1
-                x[jj] = j0 + jj < k ? ld16<NTL>(src + (uint64_t)(j0 + jj) * a.ss) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int jj = 0; jj < kInGroup; jj += 2) {
-                const uint32_t j = j0 + jj;
-                if (j + 1 < k) {
-                    Idx ia[4], ib[4];
-                    split4(ia, x[jj]);
-                    split4(ib, x[jj + 1]);
-#pragma unroll
-                    for (int r = 0; r < MAXM; ++r)
-                        if (r < (int)m) mac2(acc[r], ia, ib, tabs + r * k + j, tabs + r * k + j + 1);
-                } else if (j < k) {
-                    Idx ia[4];
-                    split4(ia, x[jj]);
-#pragma unroll
-                    for (int r = 0; r < MAXM; ++r)
-                        if (r < (int)m) mac1(acc[r], ia, tabs + r * k + j);
-                }
-            }
+            load_shards(x, src, a.ss, j0, k);
+            fold_group<MAXM>(acc, x, m, tabs, k, j0, k);
         }
         uint8_t* dst = a.out + (uint64_t)b * a.out_bs + (uint64_t)c * kChunk;
         const uint32_t nb = L.len[g] - c * kChunk;   // >= 1: chunk c starts below the block's length

@@ -50,6 +50,8 @@ __device__ __forceinline__ void recon_item(const ReconArgs& a, const uint8_t* P,
                         ? ld16<kNT>(slot_addr(dblk, pbase, slot, k, (uint32_t)a.ss, (uint32_t)a.pss))
                         : make_uint4(0, 0, 0, 0);
         }
+        // fold_group (fec_device.hpp) written out: through the helper the profiled routed kernel
+        // compiles to other code (same instruction count, a scalar compare placed differently)
 #pragma unroll
         for (int jj = 0; jj < kInGroup; jj += 2) {
             const uint32_t j = j0 + jj;

@@ -2,7 +2,7 @@
 // the plan record of one block, built by a function the plan kernel and the host self-test both
 // run, and the launch interface of fec_some.hip. Records use the wide decode's layout and its
 // Lagrange arithmetic (fec_wide.hpp): nothing in wide_coef assumes that the shard it evaluates is
-// a data shard.
+// a data shard. The rebuild is the wide decode's tile itself (launch_rs_rebuild_wide, some = true).
 #pragma once
 
 #include <stddef.h>
@@ -68,21 +68,6 @@ struct SomePlanArgs {
     WideLayout lay;
 };
 
-// The wide rebuild's tile (fec_wide.hpp WideReconArgs), writing into both regions.
-struct SomeReconArgs {
-    uint8_t* data;
-    uint8_t* parity;
-    uint64_t dbs, pbs;
-    uint32_t ss;
-    const uint8_t* plans;
-    WideLayout lay;
-    uint32_t k, len, cps, nblocks;
-    uint32_t g, c, tk;
-    uint32_t nctiles, ntiles;
-    FastDiv div_c, div_nct;
-};
-
 hipError_t launch_rs_plan_some(const SomePlanArgs& a, hipStream_t s);
-hipError_t launch_rs_rebuild_some(const SomeReconArgs& a, hipStream_t s);
 
 }  // namespace fk

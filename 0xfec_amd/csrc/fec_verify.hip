@@ -20,16 +20,8 @@ namespace fk {
 template <int MAXM, bool LDS_TABS>
 __global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const gf::PermTab* tabs;
-    if constexpr (LDS_TABS) {
-        uint32_t* dst = reinterpret_cast<uint32_t*>(smem);
-        const uint32_t nw = a.m * a.k * 8;
-        for (uint32_t i = threadIdx.x; i < nw; i += kThreads) dst[i] = a.tabs[i];
-        __syncthreads();
-        tabs = reinterpret_cast<const gf::PermTab*>(smem);
-    } else {
-        tabs = reinterpret_cast<const gf::PermTab*>(a.tabs);
-    }
+    const gf::PermTab* tabs = stage_tabs<LDS_TABS>(a.tabs, a.m * a.k * 8, smem);
+    if constexpr (LDS_TABS) __syncthreads();
     const uint32_t k = a.k, m = a.m;
     // the grid is exactly the items' workgroups; a lane past the end repeats the last item and
     // reports nothing, so every lane of a wave reaches the ballots below
@@ -48,27 +40,8 @@ __global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs a) {
     }
     for (uint32_t j0 = 0; j0 < k; j0 += kInGroup) {
         uint4 x[kInGroup];
-#pragma unroll
-        for (int jj = 0; jj < kInGroup; ++jj)   // uniform predicate: no loads past shard k-1
-            x[jj] = j0 + jj < k ? ld16<true>(src + (uint64_t)(j0 + jj) * a.ss) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int jj = 0; jj < kInGroup; jj += 2) {
-            const uint32_t j = j0 + jj;
-            if (j + 1 < k) {
-                Idx ia[4], ib[4];
-                split4(ia, x[jj]);
-                split4(ib, x[jj + 1]);
-#pragma unroll
-                for (int r = 0; r < MAXM; ++r)
-                    if (r < (int)m) mac2(acc[r], ia, ib, tabs + r * k + j, tabs + r * k + j + 1);
-            } else if (j < k) {
-                Idx ia[4];
-                split4(ia, x[jj]);
-#pragma unroll
-                for (int r = 0; r < MAXM; ++r)
-                    if (r < (int)m) mac1(acc[r], ia, tabs + r * k + j);
-            }
-        }
+        load_shards(x, src, a.ss, j0, k);
+        fold_group<MAXM>(acc, x, m, tabs, k, j0, k);
     }
     uint4 d = make_uint4(0, 0, 0, 0);
 #pragma unroll

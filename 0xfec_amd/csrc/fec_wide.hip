@@ -106,6 +106,13 @@ __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) 
 // two workgroups fit a CU's 160 KiB). Rows past a block's own erasure count carry zero tables;
 // each wave folds only the rows some block of it needs (wave_rows), and a pass runs only while
 // some block of the tile needs it. Every lane of the workgroup reaches every barrier.
+// The one variable part is where rebuilt row r goes. SOME = false (wide reconstruct / recover; the
+// outputs are erased data shards): a.out's slot r if a.out is set, else the shard's data slot.
+// SOME = true (reconstruct-some, fec_some.hip; outputs are data and parity shards alike): shard o's
+// own slot, in the data region below k and in the parity region from k on. A block's inputs
+// (present shards) and outputs (missing ones) are disjoint slots and a lane reads and writes its own
+// chunk column only, so a later row pass reads what no earlier one wrote.
+template <bool SOME>
 __global__ __launch_bounds__(kThreads) void rs_rebuild_wide_kernel(WideReconArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t k = a.k, G = a.g, TK = a.tk;
@@ -174,37 +181,28 @@ __global__ __launch_bounds__(kThreads) void rs_rebuild_wide_kernel(WideReconArgs
                                     ? ld16<kNT>(slot_addr(dblk, pbase, slot, k, a.ss, a.ss))
                                     : make_uint4(0, 0, 0, 0);
                     }
-#pragma unroll
-                    for (int jj = 0; jj < kInGroup; jj += 2) {
-                        const uint32_t j = jg + jj;
-                        if (j + 1 < tkc) {
-                            Idx ia[4], ib[4];
-                            split4(ia, x[jj]);
-                            split4(ib, x[jj + 1]);
-#pragma unroll
-                            for (int r = 0; r < (int)kWideRowPass; ++r)
-                                if (r < (int)rows) mac2(acc[r], ia, ib, T + r * TK + j, T + r * TK + j + 1);
-                        } else if (j < tkc) {
-                            Idx ia[4];
-                            split4(ia, x[jj]);
-#pragma unroll
-                            for (int r = 0; r < (int)kWideRowPass; ++r)
-                                if (r < (int)rows) mac1(acc[r], ia, T + r * TK + j);
-                        }
-                    }
+                    fold_group<(int)kWideRowPass>(acc, x, rows, T, TK, jg, tkc);
                 }
             }
         }
         if (my) {
             const uint32_t nb = a.len - chunk * kChunk;
             const uint8_t* O = H + lay.out_off + r0;
-            uint8_t* oblk = a.out ? a.out + (uint64_t)blk * a.out_bs + (uint64_t)chunk * kChunk + (uint64_t)r0 * a.ss
-                                  : nullptr;
+            uint8_t* oblk = !SOME && a.out
+                                ? a.out + (uint64_t)blk * a.out_bs + (uint64_t)chunk * kChunk + (uint64_t)r0 * a.ss
+                                : nullptr;
 #pragma unroll
             for (int r = 0; r < (int)kWideRowPass; ++r)
-                if (r < (int)my)
-                    store_chunk<kNT>(oblk ? oblk + (uint64_t)r * a.ss : dblk + (uint64_t)O[r] * a.ss,
-                                     as_uint4(acc[r]), nb);
+                if (r < (int)my) {
+                    uint8_t* dst;
+                    if constexpr (SOME) {
+                        const uint32_t o = O[r];   // (the parity region is the caller's to write here)
+                        dst = (o < k ? dblk : const_cast<uint8_t*>(pbase)) + (uint64_t)o * a.ss;
+                    } else {
+                        dst = oblk ? oblk + (uint64_t)r * a.ss : dblk + (uint64_t)O[r] * a.ss;
+                    }
+                    store_chunk<kNT>(dst, as_uint4(acc[r]), nb);
+                }
         }
     }
 }
@@ -216,10 +214,11 @@ hipError_t launch_rs_plan_wide(const WidePlanArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_rs_rebuild_wide(const WideReconArgs& a, hipStream_t s) {
+hipError_t launch_rs_rebuild_wide(const WideReconArgs& a, bool some, hipStream_t s) {
     if (a.ntiles == 0) return hipSuccess;
     const size_t lds = wide_recon_lds(a.g, a.tk, a.lay);
-    hipLaunchKernelGGL(rs_rebuild_wide_kernel, dim3(a.ntiles), dim3(kThreads), lds, s, a);
+    if (some) hipLaunchKernelGGL(rs_rebuild_wide_kernel<true>, dim3(a.ntiles), dim3(kThreads), lds, s, a);
+    else hipLaunchKernelGGL(rs_rebuild_wide_kernel<false>, dim3(a.ntiles), dim3(kThreads), lds, s, a);
     return hipGetLastError();
 }
 

@@ -77,7 +77,7 @@ struct WidePlanArgs {
 // lane per (block, chunk)); PermTabs of 16 rows x tk inputs of each block are in LDS at a time.
 struct WideReconArgs {
     uint8_t* data;
-    const uint8_t* parity;
+    const uint8_t* parity;     // read only, but for reconstruct-some, which rebuilds parity shards too
     uint64_t dbs, pbs;
     uint32_t ss;
     const uint8_t* plans;
@@ -106,6 +106,8 @@ inline size_t wide_recon_lds(uint32_t g, uint32_t tk, const WideLayout& lay) {
 }
 
 hipError_t launch_rs_plan_wide(const WidePlanArgs& a, hipStream_t s);
-hipError_t launch_rs_rebuild_wide(const WideReconArgs& a, hipStream_t s);
+// some: the reconstruct-some form of the tile (records of fec_some.hpp; rebuilt shards go to their own
+// slots in the data and the parity region, a.out unused), else the wide reconstruct / recover form.
+hipError_t launch_rs_rebuild_wide(const WideReconArgs& a, bool some, hipStream_t s);
 
 }  // namespace fk

@@ -90,3 +90,51 @@ def test_store_policy_follows_region_hulls(fec):
     # batches nt, knob st_pol 2 sc1 always (no device needed: addresses are only compared)
     lib = ctypes.CDLL(fec._LIB_PATH)
     assert lib.fec__selftest_store_policy() == 0
+
+
+def test_batch_calls_check_arguments_in_the_documented_order(fec):
+    """Every check of the 13 batch entry points that runs before the ctx is looked at, by calling
+    them with a null ctx (no device needed): the shard counts, then k + m against the call's limit,
+    then the flags the call accepts, then shard_len (0, then above 2^30), then out_slots and
+    mask_words (fec_hip.h); pairs of bad arguments pin which check wins. Arguments that pass them
+    all reach the ctx check: FEC_ERR_INVALID_ARG."""
+    from capi_calls import CALLS, layout
+    INV, NUM, MAX, NODATA = (fec.FEC_ERR_INVALID_ARG, fec.FEC_ERR_INV_SHARD_NUM, fec.FEC_ERR_MAX_SHARD_NUM,
+                             fec.FEC_ERR_SHARD_NO_DATA)
+    for call in CALLS:
+        F = getattr(fec.lib, call.name)
+        has = lambda f: f in call.tail   # noqa: E731
+        over = dict(k=call.max_n) if call.xor else dict(k=call.max_n - 1, m=2)   # k + m one above the limit
+        host = INV if not call.host else None   # a host flag: refused, or on to the next check
+        cases = [
+            ({}, INV),
+            (dict(k=0), NUM), (dict(k=-1), NUM), (over, MAX),
+            (dict(k=call.max_n - 1, m=1), INV),   # the limit itself passes
+            (dict(flags=3), INV), (dict(flags=-1), INV), (dict(flags=1), INV), (dict(flags=2), INV),
+            (dict(shard_len=0), NODATA), (dict(shard_len=(1 << 30) + 1), INV), (dict(shard_len=1 << 30), INV),
+            (dict(k=0, **{f: v for f, v in over.items() if f != "k"}), NUM),
+            (dict(k=0, flags=3), NUM), (dict(k=0, shard_len=0), NUM),
+            (dict(flags=3, **over), MAX), (dict(shard_len=0, **over), MAX),
+            (dict(flags=3, shard_len=0), INV),
+            (dict(flags=1, shard_len=0), host or NODATA), (dict(flags=2, shard_len=0), host or NODATA),
+        ]
+        if not call.xor:
+            cases += [(dict(m=-1), NUM), (dict(k=300, m=-1), NUM), (dict(m=-1, flags=3), NUM),
+                      (dict(m=-1, shard_len=0), NUM)]
+        if has("out_slots"):
+            cases += [(dict(out_slots=0), INV), (dict(out_slots=-1), INV), (dict(out_slots=0, shard_len=0), NODATA),
+                      (dict(out_slots=0, **over), MAX)]
+        if has("mask_words"):
+            cases += [(dict(mask_words=0), INV), (dict(mask_words=9), INV), (dict(k=30, m=10, mask_words=1), INV),
+                      (dict(k=200, m=56, mask_words=7), INV), (dict(k=200, m=56, mask_words=8), INV),
+                      (dict(mask_words=9, shard_len=0), NODATA), (dict(mask_words=9, flags=3), INV),
+                      (dict(mask_words=9, k=0), NUM), (dict(mask_words=9, **over), MAX),
+                      # one word and a narrow code: the forward to the narrow call, same codes
+                      (dict(mask_words=1), INV), (dict(mask_words=1, shard_len=0), NODATA),
+                      (dict(mask_words=2, shard_len=0), NODATA)]
+        for over_v, want in cases:
+            v = dict(ctx=None, k=3, m=2, shard_len=17, nblocks=1, data=None, data_bs=0, parity=None, parity_bs=0,
+                     ss=32, mask=None, status=None, lens=None, want=None, count=None, out=None, out_bs=0,
+                     out_slots=1, mask_words=1, flags=fec.FEC_DEVICE)
+            v.update(over_v)
+            assert F(*layout(call, v)) == want, (call.name, over_v)
