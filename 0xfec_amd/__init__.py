@@ -82,6 +82,8 @@ lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp
                                             _i]
 lib.fec_rs_verify_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_reconstruct_some_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
+lib.fec_rs_update_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
+lib.fec_rs_encode_idx_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
 lib.fec_xor_encode_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_xor_reconstruct_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 _u64 = ctypes.c_uint64
@@ -518,6 +520,60 @@ class Codec:
         return _check(self.rs_reconstruct_some_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity),
                                                    m * S, S, self._words_addr(masks, B, "masks"), wa, sa),
                       "fec_rs_reconstruct_some_batch")
+
+    # ---- update and encode-idx (klauspost Update / EncodeIdx; FEC_DEVICE only; device tensors): parity
+    # is changed in place by the columns each block's mask names. masks is a 4-byte integer device
+    # tensor [B, W], FEC_MASK_WORDS(k) <= W <= 8, column j = bit j % 32 of word j // 32 (wide_masks()
+    # builds it). Neither call copies new data over old. The raw mirrors return the C return code.
+    def rs_update_raw(self, k, m, shard_len, nblocks, old, old_bs, new, new_bs, parity, pbs, ss, masks, mask_words,
+                      flags=FEC_DEVICE):
+        return lib.fec_rs_update_batch(self._h, k, m, shard_len, nblocks, old, old_bs, new, new_bs, parity, pbs, ss,
+                                       masks, mask_words, flags)
+
+    def rs_encode_idx_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks, mask_words,
+                          flags=FEC_DEVICE):
+        return lib.fec_rs_encode_idx_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks,
+                                           mask_words, flags)
+
+    def _col_masks(self, masks, B):
+        W = self._mask_shape(masks, B)
+        return self._dev_some(masks), W
+
+    def rs_update(self, k, m, shards, new_data, masks, shard_len=None):
+        """shards [B, k+m, S] holds the old data and the parity (changed in place), new_data [B, k, S]."""
+        B, n, S = _shape3(shards)
+        assert n == k + m and tuple(_shape3(new_data)) == (B, k, S)
+        a = self._dev_some(shards)
+        ma, W = self._col_masks(masks, B)
+        L = S if shard_len is None else shard_len
+        return _check(self.rs_update_raw(k, m, L, B, a, n * S, self._dev_some(new_data), k * S, a + k * S, n * S, S,
+                                         ma, W), "fec_rs_update_batch")
+
+    def rs_update_split(self, k, m, old, new, parity, masks, shard_len=None):
+        B, kk, S = _shape3(old)
+        assert kk == k and tuple(_shape3(new)) == (B, k, S) and tuple(_shape3(parity)) == (B, m, S)
+        ma, W = self._col_masks(masks, B)
+        L = S if shard_len is None else shard_len
+        return _check(self.rs_update_raw(k, m, L, B, self._dev_some(old), k * S, self._dev_some(new), k * S,
+                                         self._dev_some(parity), m * S, S, ma, W), "fec_rs_update_batch")
+
+    def rs_encode_idx(self, k, m, shards, masks, shard_len=None):
+        """shards [B, k+m, S]: the masked data columns are folded into the parity slots."""
+        B, n, S = _shape3(shards)
+        assert n == k + m
+        a = self._dev_some(shards)
+        ma, W = self._col_masks(masks, B)
+        L = S if shard_len is None else shard_len
+        return _check(self.rs_encode_idx_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, ma, W),
+                      "fec_rs_encode_idx_batch")
+
+    def rs_encode_idx_split(self, k, m, data, parity, masks, shard_len=None):
+        B, kk, S = _shape3(data)
+        assert kk == k and tuple(_shape3(parity)) == (B, m, S)
+        ma, W = self._col_masks(masks, B)
+        L = S if shard_len is None else shard_len
+        return _check(self.rs_encode_idx_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity), m * S,
+                                             S, ma, W), "fec_rs_encode_idx_batch")
 
     # ---- synthetic workload on the device (include/fec_synth.h; same bytes as shard.py)
     def synth_data(self, seed, first_block, nblocks, k, payload_len, data, block_stride, shard_stride):

@@ -24,6 +24,7 @@
 #include "fec_kernels.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
+#include "fec_update.hpp"
 #include "fec_verify.hpp"
 #include "fec_wide.hpp"
 #include "gf256.h"
@@ -580,6 +581,60 @@ static int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks
             a.count = count;
             HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
         }
+        return FEC_OK;
+    });
+}
+
+// Update and encode-idx (fec_update.hip): the regions and masks of one call. `in` is the data folded
+// in (update: the new version), `old` the old version (encode-idx: null).
+struct UpdateCall {
+    const uint8_t* in;
+    size_t in_bs;
+    const uint8_t* old;
+    size_t old_bs;
+    uint8_t* parity;
+    size_t pbs, ss;
+    const uint32_t* masks;
+    size_t mask_words;
+};
+
+// The arguments of one launch: blocks [b0, b0 + nb) of the call, the pass of up to 16 parity rows
+// from r0. No device work (fec__selftest_update_slices calls it without one).
+static void fill_update_launch(fk::UpdateArgs& a, const Code* code, int r0, size_t b0, size_t nb, size_t len,
+                               const UpdateCall& u) {
+    const uint32_t cps = chunks_of(len);
+    fill_row_pass(a, code, r0, u.in + b0 * u.in_bs, u.in_bs, u.ss);
+    a.old = u.old ? u.old + b0 * u.old_bs : nullptr;
+    a.old_bs = u.old_bs;
+    a.par = u.parity + b0 * u.pbs + (size_t)r0 * u.ss;
+    a.par_bs = u.pbs;
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.total = (uint32_t)(nb * cps);
+    a.nblocks = (uint32_t)nb;
+    a.div_cps = fk::make_fastdiv(cps);
+    a.masks = u.masks + b0 * u.mask_words;
+    a.mask_words = (uint32_t)u.mask_words;
+}
+
+// emit(args) for every launch of a call: the encode's cut under kMaxItems items, parity rows in
+// passes of 16 (each pass reads the masked columns again), until one fails.
+template <class F>
+static int update_launches(const Code* code, size_t len, size_t nblocks, const UpdateCall& u, F emit) {
+    return for_slices(nblocks, blocks_per_launch(nblocks, chunks_of(len)), [&](size_t b0, size_t nb) -> int {
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::UpdateArgs a{};
+            fill_update_launch(a, code, r0, b0, nb, len, u);
+            const int rc = emit(a);
+            if (rc) return rc;
+        }
+        return FEC_OK;
+    });
+}
+
+static int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const UpdateCall& u) {
+    return update_launches(code, len, nblocks, u, [&](const fk::UpdateArgs& a) -> int {
+        HIP_TRY(fk::launch_rs_update(a, flat_grid(a.total), ctx->stream));
         return FEC_OK;
     });
 }
@@ -1658,12 +1713,14 @@ struct Call {
     bool rs = true;            // the code's tables are needed (not for XOR)
     bool encode = false;       // m == 0 leaves nothing to do
     bool null_arg = false;     // some further pointer the call needs is null
-    bool has_out = false;      // recover calls: the out region and its slot count
+    bool has_out = false;      // recover calls: the out region and its slot count (the update call: its
+                               // third region, the old data)
     const uint8_t* out = nullptr;
     size_t obs = 0;
     int out_slots = 1;
     bool wide = false;         // wide calls: words per present mask
     size_t mask_words = 1;
+    int mask_n = 0;            // the shards a mask covers (0: k + m; the update calls' column masks: k)
     struct {
         const void *a, *b;
     } words[2] = {};           // (mask, status)-like pairs of 4-byte arrays, either may be null
@@ -1677,7 +1734,8 @@ static int check_call(fec_ctx* ctx, const Call& c, Code** code) {
         return FEC_ERR_INVALID_ARG;
     if (c.len == 0) return FEC_ERR_SHARD_NO_DATA;
     if (c.len > (size_t(1) << 30) || c.out_slots <= 0) return FEC_ERR_INVALID_ARG;
-    if (c.wide && (c.mask_words < (size_t)FEC_MASK_WORDS(c.k + c.m) || c.mask_words > 8)) return FEC_ERR_INVALID_ARG;
+    if (c.wide && (c.mask_words < (size_t)FEC_MASK_WORDS(c.mask_n ? c.mask_n : c.k + c.m) || c.mask_words > 8))
+        return FEC_ERR_INVALID_ARG;
     int rc = select_device(ctx);
     if (rc) return rc;
     if (c.rs && (rc = get_code(ctx, c.k, c.m, code))) return rc;
@@ -1821,6 +1879,95 @@ int fec_rs_reconstruct_some_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
     return rs_reconstruct_some_device(ctx, k, m, shard_len, nblocks, data, data_block_stride,
                                       const_cast<uint8_t*>(par), parity_block_stride, shard_stride, present_mask,
                                       want_mask, block_status, ctx->d_err);
+}
+
+// ---------------------------------------------------------------- update, encode-idx
+// The two calls differ in the old region alone. The Call's data region is the data folded in (the
+// new version), its out region the old version: the layouts are checked in the order new data,
+// parity, old data.
+static int rs_update_call(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, bool has_old,
+                          const uint8_t* old_data, size_t old_block_stride, const uint8_t* data,
+                          size_t data_block_stride, uint8_t* parity, size_t parity_block_stride, size_t shard_stride,
+                          const uint32_t* mask, size_t mask_words, int flags) {
+    const uint8_t* par = parity;
+    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &par, parity_block_stride,
+           shard_stride};
+    c.encode = true;
+    c.null_arg = !mask || (has_old && !old_data);
+    if (has_old) c.has_out = true, c.out = old_data, c.obs = old_block_stride;
+    c.wide = true, c.mask_words = mask_words, c.mask_n = k;
+    c.words[0] = {mask, nullptr};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_update_device(ctx, code, shard_len, nblocks,
+                            {data, data_block_stride, has_old ? old_data : nullptr, old_block_stride, parity,
+                             parity_block_stride, shard_stride, mask, mask_words});
+}
+
+int fec_rs_update_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* old_data,
+                        size_t old_block_stride, const uint8_t* new_data, size_t new_block_stride, uint8_t* parity,
+                        size_t parity_block_stride, size_t shard_stride, const uint32_t* changed_mask,
+                        size_t mask_words, int flags) {
+    return rs_update_call(ctx, k, m, shard_len, nblocks, true, old_data, old_block_stride, new_data, new_block_stride,
+                          parity, parity_block_stride, shard_stride, changed_mask, mask_words, flags);
+}
+
+int fec_rs_encode_idx_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
+                            size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
+                            size_t shard_stride, const uint32_t* idx_mask, size_t mask_words, int flags) {
+    return rs_update_call(ctx, k, m, shard_len, nblocks, false, nullptr, 0, data, data_block_stride, parity,
+                          parity_block_stride, shard_stride, idx_mask, mask_words, flags);
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the launches of an update call
+// that the launch limit cuts. k = 5, m = 20, 70 000-byte shards (4375 chunks), one block more than
+// kMaxItems / 4375: two launches (490 853 blocks, then one) of two row passes each (16 rows, then
+// 4). Every launch's three region bases, mask pointer, item count, row count and table base are
+// compared with values worked out here from the call's strides, without the functions under test.
+// 0 on success, else 10 * (launch index + 1) + the failing field.
+int fec__selftest_update_slices(void) {
+    const int k = 5, m = 20;
+    const size_t L = 70000, cps = 4375, per = 490853, B = per + 1, W = 3;
+    if (per != (size_t)(kMaxItems / cps)) return 1;
+    const size_t ss = 70016, in_bs = k * ss + 48, old_bs = k * ss + 16, pbs = m * ss + 32;
+    const uintptr_t in0 = uintptr_t(1) << 40, old0 = uintptr_t(2) << 40, par0 = uintptr_t(3) << 40,
+                    mask0 = uintptr_t(4) << 40, tab0 = uintptr_t(5) << 40;
+    Code code;
+    code.k = k;
+    code.m = m;
+    code.d_tabs = (uint32_t*)tab0;
+    const UpdateCall u{(const uint8_t*)in0, in_bs, (const uint8_t*)old0, old_bs, (uint8_t*)par0, pbs, ss,
+                       (const uint32_t*)mask0, W};
+    std::vector<fk::UpdateArgs> got;
+    const int rc = update_launches(&code, L, B, u, [&](const fk::UpdateArgs& a) -> int {
+        got.push_back(a);
+        return FEC_OK;
+    });
+    code.d_tabs = nullptr;
+    if (rc != FEC_OK || got.size() != 4) return 2;
+    for (size_t i = 0; i < 4; ++i) {
+        const fk::UpdateArgs& a = got[i];
+        const int fail = 10 * ((int)i + 1);
+        const size_t b0 = (i / 2) * per, nb = i / 2 ? 1 : per, r0 = (i % 2) * 16;
+        if ((uintptr_t)a.in != in0 + b0 * in_bs || a.in_bs != in_bs) return fail + 1;
+        if ((uintptr_t)a.old != old0 + b0 * old_bs || a.old_bs != old_bs) return fail + 2;
+        if ((uintptr_t)a.par != par0 + b0 * pbs + r0 * ss || a.par_bs != pbs || a.ss != ss) return fail + 3;
+        if ((uintptr_t)a.masks != mask0 + b0 * W * 4 || a.mask_words != W) return fail + 4;
+        if (a.total != nb * cps || a.nblocks != nb || a.cps != cps || a.len != L) return fail + 5;
+        if (a.k != (uint32_t)k || a.m != (i % 2 ? 4u : 16u)) return fail + 6;
+        if ((uintptr_t)a.tabs != tab0 + r0 * k * 8 * 4) return fail + 7;
+        if (a.div_cps.d != cps) return fail + 8;
+    }
+    // encode-idx: no old region in any launch
+    UpdateCall e = u;
+    e.old = nullptr;
+    fk::UpdateArgs a{};
+    code.d_tabs = (uint32_t*)tab0;
+    fill_update_launch(a, &code, 16, per, 1, L, e);
+    code.d_tabs = nullptr;
+    if (a.old != nullptr || (uintptr_t)a.in != in0 + per * in_bs) return 3;
+    return 0;
 }
 
 // Internal self-test (not part of the public ABI, no device needed): the records some_plan_record

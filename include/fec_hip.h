@@ -29,6 +29,12 @@
  *                               Encoder.Reconstruct (want_mask NULL) and Encoder.ReconstructSome, in
  *                               place: missing parity shards are rebuilt too (klauspost's interface;
  *                               the reference calls ReconstructData only)
+ *   fec_rs_update_batch         Encoder.Update(shards, newDatashards), batched: parity repaired from the
+ *                               old and new versions of a block's changed data shards alone (klauspost's
+ *                               interface; the reference does not call it)
+ *   fec_rs_encode_idx_batch     Encoder.EncodeIdx(dataShard, idx, parity), batched and for any set of
+ *                               columns per call: parity accumulates as data shards arrive (klauspost's
+ *                               interface; the streaming sender's block fill, manager.go:123-158)
  *   fec_xor_encode_batch        xorScheme.xor loop          internal/fec/xor.go:28-33,44-56
  *   fec_xor_reconstruct_batch   xorScheme recover loops     internal/fec/xor.go:80-86
  *
@@ -306,6 +312,63 @@ int fec_rs_reconstruct_some_batch(fec_ctx *ctx, int k, int m, size_t shard_len, 
                                   uint8_t *parity, size_t parity_block_stride,
                                   size_t shard_stride, const uint32_t *present_mask,
                                   const uint32_t *want_mask, int32_t *block_status, int flags);
+
+/* RS Update and EncodeIdx, batched: parity is changed in place from some of a block's data shards,
+ *   parity_i ^= XOR over j in C_b of M[k+i][j] * delta_j,     i = 0..m-1,
+ * where C_b is the set of columns j < k named by block b's mask, and delta_j is old_j ^ new_j
+ * (fec_rs_update_batch: data shard j changed from its old to its new version) or data_j
+ * (fec_rs_encode_idx_batch: data shard j is added to a parity that did not hold it yet).
+ *
+ * Masks. Block b's column mask is the mask_words words at mask + b*mask_words; column j is bit j % 32
+ * of word j / 32 (the wide calls' form); bits at and above k are ignored. FEC_MASK_WORDS(k) <=
+ * mask_words <= 8, else FEC_ERR_INVALID_ARG: the bound follows k, not k + m. The masks are device
+ * memory, 4-byte aligned (else FEC_ERR_ALIGNMENT).
+ *
+ * Codes. Every code the encode takes: k >= 1, m >= 0, k + m <= 256. m == 0 or nblocks == 0 returns
+ * FEC_OK and touches nothing.
+ *
+ * Per block. C_b empty: no byte of the block is read or written. Otherwise bytes [0, shard_len) of
+ * each of the m parity slots become old parity ^ the sum above, bytes [shard_len, round_up(shard_len,
+ * 16)) of each of the m parity slots are written as zeros (whole 16-byte stores, as every output
+ * shard), and nothing else is written. Of the data regions only the slots of the columns in C_b are
+ * read, over their first round_up(shard_len, 16) bytes, old and new alike; bytes at and past shard_len
+ * of any slot never influence bytes [0, shard_len) of the result. old_data and new_data are only
+ * read: the call does not copy new over old (as klauspost's Update does not). The parity region
+ * must not overlap either data region; this is not checked.
+ *
+ * klauspost's errors. EncodeIdx's idx out of range (ErrInvShardNum) has no counterpart: a bit at or
+ * above k is ignored. Update's "new shard given but old shard nil" cannot arise: every old slot
+ * exists, and the mask alone says which columns changed. As with klauspost's EncodeIdx, the parity
+ * must start as zeros (over the slots' first round_up(shard_len, 16) bytes) and each column must be
+ * added exactly once for the result to be the encode's parity; neither is checked. A full mask on
+ * zeroed parity gives byte for byte what fec_rs_encode_batch writes.
+ *
+ * FEC_DEVICE only: any other `flags` value returns FEC_ERR_INVALID_ARG. There is no host-resident
+ * form: it would move the changed shards and the parity both ways over the host link, more than a
+ * CPU update touches where the shards already are. Asynchronous on the ctx stream; the calls never
+ * touch the sticky word. The layout and alignment rules are the uniform calls', for all three
+ * regions with the one shard_stride; the host-side checks run in the uniform order: shard counts,
+ * k + m > 256, flags, shard_len (0: FEC_ERR_SHARD_NO_DATA, above 2^30: FEC_ERR_INVALID_ARG),
+ * mask_words, the ctx, nblocks == 0 or m == 0 (FEC_OK), null pointers (the mask, the data regions,
+ * parity), the layouts (new data or data, parity, old data), the mask's alignment. Batches are cut
+ * into launches as the encode cuts them, codes of m > 16 into passes of 16 parity rows, each of
+ * which reads the block's masked columns again.
+ *
+ * Cost. A call moves (c*s + 2*m) shard slots per block for c masked columns (s = 2 for update, 1 for
+ * encode-idx) where the encode moves k + m: accumulating a whole block one column at a time moves
+ * k*(1 + 2*m). The calls are for callers that hold only some of a block's shards or need the parity
+ * one fold after the last shard; they are not a faster encode. */
+int fec_rs_update_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                        const uint8_t *old_data, size_t old_block_stride,
+                        const uint8_t *new_data, size_t new_block_stride,
+                        uint8_t *parity, size_t parity_block_stride,
+                        size_t shard_stride, const uint32_t *changed_mask, size_t mask_words,
+                        int flags);
+int fec_rs_encode_idx_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                            const uint8_t *data, size_t data_block_stride,
+                            uint8_t *parity, size_t parity_block_stride,
+                            size_t shard_stride, const uint32_t *idx_mask, size_t mask_words,
+                            int flags);
 
 /* XOR(k, 1) encode: parity = XOR of the k data shards. */
 int fec_xor_encode_batch(fec_ctx *ctx, int k, size_t shard_len, size_t nblocks,
