@@ -9,6 +9,7 @@ Import by name (the directory starts with a digit):
     fec = importlib.import_module("0xfec_amd")
 """
 import ctypes
+import functools
 import os
 
 # PyTorch-ROCm ships its own libamdhip64.so (same SONAME, libamdhip64.so.7). Loading torch
@@ -167,6 +168,57 @@ def _shape3(shards):
     return B, n, S
 
 
+def _dev(x, what):
+    """Address of x, which must lie in device memory (`what`: the assertion's message)."""
+    a, kind = _addr(x)
+    assert kind == FEC_DEVICE, what
+    return a
+
+
+def _opt(x, dev_only=None):
+    """Address of an optional array (None for None); dev_only: as _dev's message."""
+    if x is None:
+        return None
+    return _addr(x)[0] if dev_only is None else _dev(x, dev_only)
+
+
+_RAGGED = "the ragged calls take device memory only"
+_SOME = "verify and reconstruct-some take device memory only"
+
+
+class _Layout:
+    """Where the batch of one call lies, resolved once for both forms of every method: interleaved
+    shards [B, k+m, S] (parity None), or split data [B, k, S] and parity [B, m, S] in separate
+    buffers of one memory kind. B blocks of S-byte slots, data at address d and parity at p with
+    block strides dbs and pbs, memory kind `kind`. dev_only: the message of the assertion that the
+    batch lies in device memory, for the calls that take nothing else."""
+
+    def __init__(self, k, m, shards, parity=None, dev_only=None):
+        self.B, n, self.S = _shape3(shards)
+        self.d, self.kind = _addr(shards)
+        if parity is None:
+            assert n == k + m
+            self.dbs = self.pbs = n * self.S
+            self.p = self.d + k * self.S
+        else:
+            assert n == k and tuple(_shape3(parity)) == (self.B, m, self.S)
+            self.dbs, self.pbs = k * self.S, m * self.S
+            self.p, pkind = _addr(parity)
+            assert pkind == self.kind
+        assert dev_only is None or self.kind == FEC_DEVICE, dev_only
+
+    def args(self, shard_len):
+        """The C calls' shard_len (default S), nblocks, data, data_block_stride, parity,
+        parity_block_stride, shard_stride."""
+        return (self.S if shard_len is None else shard_len, self.B, self.d, self.dbs, self.p, self.pbs, self.S)
+
+    def out(self, out, dev_only=None):
+        """A recover call's out [B, slots, S]: its address, out_block_stride, out_slots."""
+        B, slots, S = _shape3(out)
+        assert (B, S) == (self.B, self.S)
+        return _opt(out, dev_only), slots * S, slots
+
+
 class Codec:
     """One device context (one HIP stream). Batch entry points over [B, n, S] uint8 arrays:
     numpy arrays and pageable CPU tensors run the FEC_HOST path (staged through pinned memory),
@@ -255,53 +307,37 @@ class Codec:
                                             masks, status, flags)
 
     # ---- array conveniences. Interleaved form: shards is [B, k+m, S]. Split form: data
-    # [B, k, S] and parity [B, m, S] in separate buffers. shard_len defaults to S.
+    # [B, k, S] and parity [B, m, S] in separate buffers. shard_len defaults to S. Each operation
+    # is written once, against the _Layout of either form.
+    def _encode(self, k, m, lay, shard_len):
+        return self.rs_encode_raw(k, m, *lay.args(shard_len), lay.kind)
+
     def rs_encode(self, k, m, shards, shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a, kind = _addr(shards)
-        L = S if shard_len is None else shard_len
-        return self.rs_encode_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, kind)
+        return self._encode(k, m, _Layout(k, m, shards), shard_len)
 
     def rs_encode_split(self, k, m, data, parity, shard_len=None):
-        B, kk, S = _shape3(data)
-        B2, mm, S2 = _shape3(parity)
-        assert (kk, mm, B, S) == (k, m, B2, S2)
-        d, kind = _addr(data)
-        p, kind2 = _addr(parity)
-        assert kind == kind2
-        L = S if shard_len is None else shard_len
-        return self.rs_encode_raw(k, m, L, B, d, k * S, p, m * S, S, kind)
+        return self._encode(k, m, _Layout(k, m, data, parity), shard_len)
 
-    def _recon(self, fn, what, k, m, B, S, d, dbs, p, pbs, kind, masks, status, shard_len):
+    def _recon(self, fn, lay, masks, status, shard_len, *mask_words):
+        """fn: a C reconstruct call with its arguments before shard_len bound. Returns its return
+        code for FEC_OK and FEC_ERR_TOO_FEW_SHARDS, raises for any other."""
         ma, mkind = _addr(masks)
-        assert (mkind == FEC_DEVICE) == (kind == FEC_DEVICE), "masks must live where the shards live"
-        sa = _addr(status)[0] if status is not None else None
-        L = S if shard_len is None else shard_len
-        rc = fn(B, L, d, dbs, p, pbs, S, ma, sa, kind)
+        assert (mkind == FEC_DEVICE) == (lay.kind == FEC_DEVICE), "masks must live where the shards live"
+        rc = fn(*lay.args(shard_len), ma, *mask_words, _opt(status), lay.kind)
         if rc not in (FEC_OK, FEC_ERR_TOO_FEW_SHARDS):
-            _check(rc, what)
+            _check(rc, fn.func.__name__)
         return rc
+
+    def _reconstruct(self, k, m, lay, masks, status, shard_len):
+        return self._recon(functools.partial(lib.fec_rs_reconstruct_batch, self._h, k, m), lay, masks, status,
+                           shard_len)
 
     def rs_reconstruct(self, k, m, shards, masks, status=None, shard_len=None):
         """Returns the C return code (FEC_OK or FEC_ERR_TOO_FEW_SHARDS for FEC_HOST)."""
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a, kind = _addr(shards)
-        fn = lambda B_, L, d, dbs, p, pbs, ss, ma, sa, kd: lib.fec_rs_reconstruct_batch(
-            self._h, k, m, L, B_, d, dbs, p, pbs, ss, ma, sa, kd)
-        return self._recon(fn, "fec_rs_reconstruct_batch", k, m, B, S, a, n * S, a + k * S, n * S, kind,
-                           masks, status, shard_len)
+        return self._reconstruct(k, m, _Layout(k, m, shards), masks, status, shard_len)
 
     def rs_reconstruct_split(self, k, m, data, parity, masks, status=None, shard_len=None):
-        B, kk, S = _shape3(data)
-        assert kk == k and tuple(parity.shape) == (B, m, S)
-        d, kind = _addr(data)
-        p, _ = _addr(parity)
-        fn = lambda B_, L, d_, dbs, p_, pbs, ss, ma, sa, kd: lib.fec_rs_reconstruct_batch(
-            self._h, k, m, L, B_, d_, dbs, p_, pbs, ss, ma, sa, kd)
-        return self._recon(fn, "fec_rs_reconstruct_batch", k, m, B, S, d, k * S, p, m * S, kind,
-                           masks, status, shard_len)
+        return self._reconstruct(k, m, _Layout(k, m, data, parity), masks, status, shard_len)
 
     def rs_recover_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks, out, out_bs, out_slots,
                        status, flags=FEC_DEVICE):
@@ -311,14 +347,9 @@ class Codec:
     def rs_recover_split(self, k, m, data, parity, masks, out, status=None, shard_len=None):
         """Rebuild the erased data shards of each block into out [B, slots, S] (ascending order);
         status[b] = number rebuilt, or a negative error code."""
-        B, kk, S = _shape3(data)
-        B2, slots, S2 = _shape3(out)
-        assert kk == k and tuple(parity.shape) == (B, m, S) and (B2, S2) == (B, S)
-        L = S if shard_len is None else shard_len
-        sa = _addr(status)[0] if status is not None else None
-        rc = self.rs_recover_raw(k, m, L, B, _addr(data)[0], k * S, _addr(parity)[0], m * S, S, _addr(masks)[0],
-                                 _addr(out)[0], slots * S, slots, sa)
-        return _check(rc, "fec_rs_recover_batch")
+        lay = _Layout(k, m, data, parity)
+        return _check(self.rs_recover_raw(k, m, *lay.args(shard_len), _addr(masks)[0], *lay.out(out), _opt(status)),
+                      "fec_rs_recover_batch")
 
     # ---- wide forms (k + m <= 256): masks are uint32 [B, W] arrays, FEC_MASK_WORDS(k + m) <= W <= 8,
     # living where the shards live; same return conventions as the narrow methods
@@ -341,40 +372,24 @@ class Codec:
             assert masks.flags.c_contiguous and masks.itemsize == 4
         return int(masks.shape[1])
 
+    def _reconstruct_wide(self, k, m, lay, masks, status, shard_len):
+        return self._recon(functools.partial(lib.fec_rs_reconstruct_wide_batch, self._h, k, m), lay, masks, status,
+                           shard_len, self._mask_shape(masks, lay.B))
+
     def rs_reconstruct_wide(self, k, m, shards, masks, status=None, shard_len=None):
         """Returns the C return code (FEC_OK or FEC_ERR_TOO_FEW_SHARDS for FEC_HOST)."""
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        W = self._mask_shape(masks, B)
-        a, kind = _addr(shards)
-        fn = lambda B_, L, d, dbs, p, pbs, ss, ma, sa, kd: lib.fec_rs_reconstruct_wide_batch(
-            self._h, k, m, L, B_, d, dbs, p, pbs, ss, ma, W, sa, kd)
-        return self._recon(fn, "fec_rs_reconstruct_wide_batch", k, m, B, S, a, n * S, a + k * S, n * S, kind,
-                           masks, status, shard_len)
+        return self._reconstruct_wide(k, m, _Layout(k, m, shards), masks, status, shard_len)
 
     def rs_reconstruct_wide_split(self, k, m, data, parity, masks, status=None, shard_len=None):
-        B, kk, S = _shape3(data)
-        assert kk == k and tuple(parity.shape) == (B, m, S)
-        W = self._mask_shape(masks, B)
-        d, kind = _addr(data)
-        p, _ = _addr(parity)
-        fn = lambda B_, L, d_, dbs, p_, pbs, ss, ma, sa, kd: lib.fec_rs_reconstruct_wide_batch(
-            self._h, k, m, L, B_, d_, dbs, p_, pbs, ss, ma, W, sa, kd)
-        return self._recon(fn, "fec_rs_reconstruct_wide_batch", k, m, B, S, d, k * S, p, m * S, kind,
-                           masks, status, shard_len)
+        return self._reconstruct_wide(k, m, _Layout(k, m, data, parity), masks, status, shard_len)
 
     def rs_recover_wide_split(self, k, m, data, parity, masks, out, status=None, shard_len=None):
         """Rebuild the erased data shards of each block into out [B, slots, S] (ascending order);
         status[b] = number rebuilt, or a negative error code."""
-        B, kk, S = _shape3(data)
-        B2, slots, S2 = _shape3(out)
-        assert kk == k and tuple(parity.shape) == (B, m, S) and (B2, S2) == (B, S)
-        W = self._mask_shape(masks, B)
-        L = S if shard_len is None else shard_len
-        sa = _addr(status)[0] if status is not None else None
-        rc = self.rs_recover_wide_raw(k, m, L, B, _addr(data)[0], k * S, _addr(parity)[0], m * S, S,
-                                      _addr(masks)[0], W, _addr(out)[0], slots * S, slots, sa)
-        return _check(rc, "fec_rs_recover_wide_batch")
+        lay = _Layout(k, m, data, parity)
+        W = self._mask_shape(masks, lay.B)
+        return _check(self.rs_recover_wide_raw(k, m, *lay.args(shard_len), _addr(masks)[0], W, *lay.out(out),
+                                               _opt(status)), "fec_rs_recover_wide_batch")
 
     # ---- ragged forms (FEC_DEVICE only): lens is a uint32 / int32 device tensor [B], block b's shard
     # length in bytes (0: the block is skipped; > max_shard_len: status FEC_ERR_SHARD_SIZE);
@@ -400,60 +415,36 @@ class Codec:
             "block lengths are a uint32 / int32 device tensor [B]"
         return lens.data_ptr()
 
-    @staticmethod
-    def _dev(x):
-        a, kind = _addr(x)
-        assert kind == FEC_DEVICE, "the ragged calls take device memory only"
-        return a
+    def _encode_ragged(self, k, m, lay, lens, status, max_shard_len):
+        return _check(self.rs_encode_ragged_raw(k, m, *lay.args(max_shard_len), self._lens_addr(lens, lay.B),
+                                                _opt(status, _RAGGED)), "fec_rs_encode_ragged_batch")
 
     def rs_encode_ragged(self, k, m, shards, lens, status=None, max_shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a = self._dev(shards)
-        L = S if max_shard_len is None else max_shard_len
-        sa = self._dev(status) if status is not None else None
-        return _check(self.rs_encode_ragged_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, self._lens_addr(lens, B),
-                                                sa), "fec_rs_encode_ragged_batch")
+        return self._encode_ragged(k, m, _Layout(k, m, shards, None, _RAGGED), lens, status, max_shard_len)
 
     def rs_encode_ragged_split(self, k, m, data, parity, lens, status=None, max_shard_len=None):
-        B, kk, S = _shape3(data)
-        B2, mm, S2 = _shape3(parity)
-        assert (kk, mm, B, S) == (k, m, B2, S2)
-        L = S if max_shard_len is None else max_shard_len
-        sa = self._dev(status) if status is not None else None
-        return _check(self.rs_encode_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
-                                                self._lens_addr(lens, B), sa), "fec_rs_encode_ragged_batch")
+        return self._encode_ragged(k, m, _Layout(k, m, data, parity, _RAGGED), lens, status, max_shard_len)
+
+    def _reconstruct_ragged(self, k, m, lay, masks, lens, status, max_shard_len):
+        return _check(self.rs_reconstruct_ragged_raw(k, m, *lay.args(max_shard_len), _dev(masks, _RAGGED),
+                                                     self._lens_addr(lens, lay.B), _opt(status, _RAGGED)),
+                      "fec_rs_reconstruct_ragged_batch")
 
     def rs_reconstruct_ragged(self, k, m, shards, masks, lens, status=None, max_shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a = self._dev(shards)
-        L = S if max_shard_len is None else max_shard_len
-        sa = self._dev(status) if status is not None else None
-        return _check(self.rs_reconstruct_ragged_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, self._dev(masks),
-                                                     self._lens_addr(lens, B), sa),
-                      "fec_rs_reconstruct_ragged_batch")
+        return self._reconstruct_ragged(k, m, _Layout(k, m, shards, None, _RAGGED), masks, lens, status,
+                                        max_shard_len)
 
     def rs_reconstruct_ragged_split(self, k, m, data, parity, masks, lens, status=None, max_shard_len=None):
-        B, kk, S = _shape3(data)
-        assert kk == k and tuple(parity.shape) == (B, m, S)
-        L = S if max_shard_len is None else max_shard_len
-        sa = self._dev(status) if status is not None else None
-        return _check(self.rs_reconstruct_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
-                                                     self._dev(masks), self._lens_addr(lens, B), sa),
-                      "fec_rs_reconstruct_ragged_batch")
+        return self._reconstruct_ragged(k, m, _Layout(k, m, data, parity, _RAGGED), masks, lens, status,
+                                        max_shard_len)
 
     def rs_recover_ragged_split(self, k, m, data, parity, masks, lens, out, status=None, max_shard_len=None):
         """Rebuild the erased data shards of each block into out [B, slots, S] (ascending order);
         status[b] = number rebuilt, or a negative error code."""
-        B, kk, S = _shape3(data)
-        B2, slots, S2 = _shape3(out)
-        assert kk == k and tuple(parity.shape) == (B, m, S) and (B2, S2) == (B, S)
-        L = S if max_shard_len is None else max_shard_len
-        sa = self._dev(status) if status is not None else None
-        return _check(self.rs_recover_ragged_raw(k, m, L, B, self._dev(data), k * S, self._dev(parity), m * S, S,
-                                                 self._dev(masks), self._lens_addr(lens, B), self._dev(out),
-                                                 slots * S, slots, sa), "fec_rs_recover_ragged_batch")
+        lay = _Layout(k, m, data, parity, _RAGGED)
+        return _check(self.rs_recover_ragged_raw(k, m, *lay.args(max_shard_len), _dev(masks, _RAGGED),
+                                                 self._lens_addr(lens, lay.B), *lay.out(out, _RAGGED),
+                                                 _opt(status, _RAGGED)), "fec_rs_recover_ragged_batch")
 
     # ---- verify and reconstruct-some (FEC_DEVICE only; device tensors). Verify: status is an int32
     # device tensor [B] (1 = the block's parity matches its data, 0 = not), count an optional
@@ -471,55 +462,34 @@ class Codec:
                                                  masks, want, status, flags)
 
     @staticmethod
-    def _dev_some(x):
-        a, kind = _addr(x)
-        assert kind == FEC_DEVICE, "verify and reconstruct-some take device memory only"
-        return a
-
-    @classmethod
-    def _words_addr(cls, x, count, what):
+    def _words_addr(x, count, what):
         assert x.numel() == count and x.is_contiguous() and x.element_size() == 4, \
             "%s is a 4-byte integer device tensor of %d element(s)" % (what, count)
-        return cls._dev_some(x)
+        return _dev(x, _SOME)
+
+    def _verify(self, k, m, lay, status, count, shard_len):
+        ca = None if count is None else self._words_addr(count, 1, "count")
+        return _check(self.rs_verify_raw(k, m, *lay.args(shard_len), self._words_addr(status, lay.B, "status"), ca),
+                      "fec_rs_verify_batch")
 
     def rs_verify(self, k, m, shards, status, count=None, shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a = self._dev_some(shards)
-        L = S if shard_len is None else shard_len
-        ca = self._words_addr(count, 1, "count") if count is not None else None
-        return _check(self.rs_verify_raw(k, m, L, B, a, n * S, a + k * S, n * S, S,
-                                         self._words_addr(status, B, "status"), ca), "fec_rs_verify_batch")
+        return self._verify(k, m, _Layout(k, m, shards, None, _SOME), status, count, shard_len)
 
     def rs_verify_split(self, k, m, data, parity, status, count=None, shard_len=None):
-        B, kk, S = _shape3(data)
-        B2, mm, S2 = _shape3(parity)
-        assert (kk, mm, B, S) == (k, m, B2, S2)
-        L = S if shard_len is None else shard_len
-        ca = self._words_addr(count, 1, "count") if count is not None else None
-        return _check(self.rs_verify_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity), m * S, S,
-                                         self._words_addr(status, B, "status"), ca), "fec_rs_verify_batch")
+        return self._verify(k, m, _Layout(k, m, data, parity, _SOME), status, count, shard_len)
+
+    def _reconstruct_some(self, k, m, lay, masks, want, status, shard_len):
+        wa = None if want is None else self._words_addr(want, lay.B, "want")
+        sa = None if status is None else self._words_addr(status, lay.B, "status")
+        return _check(self.rs_reconstruct_some_raw(k, m, *lay.args(shard_len),
+                                                   self._words_addr(masks, lay.B, "masks"), wa, sa),
+                      "fec_rs_reconstruct_some_batch")
 
     def rs_reconstruct_some(self, k, m, shards, masks, want=None, status=None, shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a = self._dev_some(shards)
-        L = S if shard_len is None else shard_len
-        wa = self._words_addr(want, B, "want") if want is not None else None
-        sa = self._words_addr(status, B, "status") if status is not None else None
-        return _check(self.rs_reconstruct_some_raw(k, m, L, B, a, n * S, a + k * S, n * S, S,
-                                                   self._words_addr(masks, B, "masks"), wa, sa),
-                      "fec_rs_reconstruct_some_batch")
+        return self._reconstruct_some(k, m, _Layout(k, m, shards, None, _SOME), masks, want, status, shard_len)
 
     def rs_reconstruct_some_split(self, k, m, data, parity, masks, want=None, status=None, shard_len=None):
-        B, kk, S = _shape3(data)
-        assert kk == k and tuple(parity.shape) == (B, m, S)
-        L = S if shard_len is None else shard_len
-        wa = self._words_addr(want, B, "want") if want is not None else None
-        sa = self._words_addr(status, B, "status") if status is not None else None
-        return _check(self.rs_reconstruct_some_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity),
-                                                   m * S, S, self._words_addr(masks, B, "masks"), wa, sa),
-                      "fec_rs_reconstruct_some_batch")
+        return self._reconstruct_some(k, m, _Layout(k, m, data, parity, _SOME), masks, want, status, shard_len)
 
     # ---- update and encode-idx (klauspost Update / EncodeIdx; FEC_DEVICE only; device tensors): parity
     # is changed in place by the columns each block's mask names. masks is a 4-byte integer device
@@ -537,43 +507,31 @@ class Codec:
 
     def _col_masks(self, masks, B):
         W = self._mask_shape(masks, B)
-        return self._dev_some(masks), W
+        return _dev(masks, _SOME), W
+
+    def _update(self, k, m, lay, new, masks, shard_len):
+        assert tuple(_shape3(new)) == (lay.B, k, lay.S)
+        L, B, old, old_bs, parity, pbs, S = lay.args(shard_len)
+        return _check(self.rs_update_raw(k, m, L, B, old, old_bs, _dev(new, _SOME), k * S, parity, pbs, S,
+                                         *self._col_masks(masks, B)), "fec_rs_update_batch")
 
     def rs_update(self, k, m, shards, new_data, masks, shard_len=None):
         """shards [B, k+m, S] holds the old data and the parity (changed in place), new_data [B, k, S]."""
-        B, n, S = _shape3(shards)
-        assert n == k + m and tuple(_shape3(new_data)) == (B, k, S)
-        a = self._dev_some(shards)
-        ma, W = self._col_masks(masks, B)
-        L = S if shard_len is None else shard_len
-        return _check(self.rs_update_raw(k, m, L, B, a, n * S, self._dev_some(new_data), k * S, a + k * S, n * S, S,
-                                         ma, W), "fec_rs_update_batch")
+        return self._update(k, m, _Layout(k, m, shards, None, _SOME), new_data, masks, shard_len)
 
     def rs_update_split(self, k, m, old, new, parity, masks, shard_len=None):
-        B, kk, S = _shape3(old)
-        assert kk == k and tuple(_shape3(new)) == (B, k, S) and tuple(_shape3(parity)) == (B, m, S)
-        ma, W = self._col_masks(masks, B)
-        L = S if shard_len is None else shard_len
-        return _check(self.rs_update_raw(k, m, L, B, self._dev_some(old), k * S, self._dev_some(new), k * S,
-                                         self._dev_some(parity), m * S, S, ma, W), "fec_rs_update_batch")
+        return self._update(k, m, _Layout(k, m, old, parity, _SOME), new, masks, shard_len)
+
+    def _encode_idx(self, k, m, lay, masks, shard_len):
+        return _check(self.rs_encode_idx_raw(k, m, *lay.args(shard_len), *self._col_masks(masks, lay.B)),
+                      "fec_rs_encode_idx_batch")
 
     def rs_encode_idx(self, k, m, shards, masks, shard_len=None):
         """shards [B, k+m, S]: the masked data columns are folded into the parity slots."""
-        B, n, S = _shape3(shards)
-        assert n == k + m
-        a = self._dev_some(shards)
-        ma, W = self._col_masks(masks, B)
-        L = S if shard_len is None else shard_len
-        return _check(self.rs_encode_idx_raw(k, m, L, B, a, n * S, a + k * S, n * S, S, ma, W),
-                      "fec_rs_encode_idx_batch")
+        return self._encode_idx(k, m, _Layout(k, m, shards, None, _SOME), masks, shard_len)
 
     def rs_encode_idx_split(self, k, m, data, parity, masks, shard_len=None):
-        B, kk, S = _shape3(data)
-        assert kk == k and tuple(_shape3(parity)) == (B, m, S)
-        ma, W = self._col_masks(masks, B)
-        L = S if shard_len is None else shard_len
-        return _check(self.rs_encode_idx_raw(k, m, L, B, self._dev_some(data), k * S, self._dev_some(parity), m * S,
-                                             S, ma, W), "fec_rs_encode_idx_batch")
+        return self._encode_idx(k, m, _Layout(k, m, data, parity, _SOME), masks, shard_len)
 
     # ---- synthetic workload on the device (include/fec_synth.h; same bytes as shard.py)
     def synth_data(self, seed, first_block, nblocks, k, payload_len, data, block_stride, shard_stride):
@@ -614,18 +572,10 @@ class Codec:
                 "duplex_each_GBps": round(out[2], 2)}
 
     def xor_encode(self, k, shards, shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + 1
-        a, kind = _addr(shards)
-        L = S if shard_len is None else shard_len
-        return _check(lib.fec_xor_encode_batch(self._h, k, L, B, a, n * S, a + k * S, n * S, S, kind),
-                      "fec_xor_encode_batch")
+        lay = _Layout(k, 1, shards)
+        return _check(lib.fec_xor_encode_batch(self._h, k, *lay.args(shard_len), lay.kind), "fec_xor_encode_batch")
 
     def xor_reconstruct(self, k, shards, masks, status=None, shard_len=None):
-        B, n, S = _shape3(shards)
-        assert n == k + 1
-        a, kind = _addr(shards)
-        fn = lambda B_, L, d, dbs, p, pbs, ss, ma, sa, kd: lib.fec_xor_reconstruct_batch(
-            self._h, k, L, B_, d, dbs, p, pbs, ss, ma, sa, kd)
-        return self._recon(fn, "fec_xor_reconstruct_batch", k, 1, B, S, a, n * S, a + k * S, n * S, kind,
-                           masks, status, shard_len)
+        return self._recon(functools.partial(lib.fec_xor_reconstruct_batch, self._h, k), _Layout(k, 1, shards), masks,
+                           status, shard_len)
+

@@ -1,0 +1,538 @@
+// fec_cores.cpp — the device-memory cores of the C ABI (fec_ctx.hpp): each cuts one call over device
+// memory into launches and fills their arguments. The FEC_DEVICE entry points (fec_capi.cpp) call
+// them on the caller's regions, the host-resident drivers (fec_host.cpp) on their staging buffers.
+#include <algorithm>
+
+#include "fec_ctx.hpp"
+#include "fec_kernels.hpp"
+#include "fec_ragged.hpp"
+#include "fec_some.hpp"
+#include "fec_update.hpp"
+#include "fec_verify.hpp"
+#include "fec_wide.hpp"
+
+// Workgroups for a flat (block, chunk) item launch: one item per lane (total < 2^31).
+static int flat_grid(uint32_t total) {
+    return (int)std::max<uint64_t>(1, ((uint64_t)total + fk::kThreads - 1) / fk::kThreads);
+}
+
+// A batch is cut into launches of consecutive blocks: fewer than kMaxItems items (block, chunk)
+// each, and, where a launch keeps a plan record of `stride` bytes per block, at most kPlanBytes of
+// records.
+static uint32_t chunks_of(size_t len) { return (uint32_t)((len + fk::kChunk - 1) / fk::kChunk); }
+
+static size_t blocks_per_launch(size_t nblocks, uint32_t cps, size_t stride = 0) {
+    size_t per = (size_t)(kMaxItems / cps);
+    if (stride) per = std::min(per, kPlanBytes / stride);
+    return std::max<size_t>(1, std::min(per, nblocks));
+}
+
+// body(b0, nb) for each launch's blocks [b0, b0 + nb), until one fails.
+template <class F>
+static int for_slices(size_t nblocks, size_t per_launch, F body) {
+    for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
+        const int rc = body(b0, std::min(per_launch, nblocks - b0));
+        if (rc) return rc;
+    }
+    return FEC_OK;
+}
+
+// What EncodeArgs, VerifyArgs and RagEncodeArgs share: the data of the launch's first block and the
+// tables of the pass of up to 16 parity rows from r0.
+template <class Args>
+static void fill_row_pass(Args& a, const Code* code, int r0, const uint8_t* data, size_t dbs, size_t ss) {
+    a.in = data;
+    a.in_bs = dbs;
+    a.ss = ss;
+    a.k = (uint32_t)code->k;
+    a.m = (uint32_t)std::min(16, code->m - r0);
+    a.tabs = code->d_tabs + (size_t)r0 * code->k * 8;
+}
+
+int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data,
+                     size_t dbs, uint8_t* parity, size_t pbs, size_t ss) {
+    const uint32_t cps = chunks_of(len);
+    const int k = code->k;
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::EncodeArgs a{};
+            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
+            a.out = parity + b0 * pbs + (size_t)r0 * ss;
+            a.out_bs = pbs;
+            a.len = (uint32_t)len;
+            a.cps = cps;
+            a.total = (uint32_t)(nb * cps);
+            a.div_cps = fk::make_fastdiv(cps);
+            a.dytabs = (r0 == 0 && (int)a.m == code->m) ? code->d_dytabs : nullptr;
+            a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {data, dbs, ss, (uint64_t)k},
+                                           {parity, pbs, ss, (uint64_t)code->m}, len, nblocks);
+            if (fk::fixed_encode_applies((uint32_t)k, a.m, a.dytabs != nullptr)) {
+                HIP_TRY(fk::launch_rs_encode_fixed(a, ctx->stream));
+                continue;
+            }
+            HIP_TRY(fk::launch_rs_encode(a, flat_grid(a.total), ctx->stream));
+        }
+        return FEC_OK;
+    });
+}
+
+// What a slice's PlanArgs and ReconArgs hold in the uniform and the ragged reconstruct alike: blocks
+// [b0, b0 + nb) of the call, records of layout `lay` in the stream's workspace, tiles of G blocks.
+struct ReconCall {
+    uint8_t* data;
+    size_t dbs;
+    const uint8_t* parity;
+    size_t pbs, ss, pss;
+    const uint32_t* masks;
+    int32_t* status;
+    int* err;
+    uint8_t* out;
+    size_t out_bs;
+    uint32_t out_slots;
+};
+static void fill_recon_slice(fk::PlanArgs& p, fk::ReconArgs& a, fec_ctx* ctx, const Code* code, const ReconCall& c,
+                             size_t len, uint32_t cps, uint32_t maxe, const fk::PlanLayout& lay, uint32_t G,
+                             size_t b0, size_t nb) {
+    p.masks = c.masks + b0;
+    p.plans = ctx->work->d_plans;
+    p.status = c.status ? c.status + b0 : nullptr;
+    p.err = c.err;
+    p.prows = code->d_prows;
+    p.k = (uint32_t)code->k;
+    p.m = (uint32_t)code->m;
+    p.nblocks = (uint32_t)nb;
+    p.maxe = maxe;
+    p.lay = lay;
+    p.max_out = c.out ? c.out_slots : 0;
+    p.dall = code->d_dall;   // (read by the sorted plans only)
+    a.data = c.data + b0 * c.dbs;
+    a.parity = c.parity + b0 * c.pbs;
+    a.dbs = c.dbs;
+    a.pbs = c.pbs;
+    a.ss = c.ss;
+    a.pss = c.pss;
+    a.plans = ctx->work->d_plans;
+    a.k = p.k;
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.nblocks = (uint32_t)nb;
+    a.maxe = maxe;
+    a.lay = lay;
+    a.g = G;
+    a.ntiles = (uint32_t)((nb + G - 1) / G);
+    a.div_cps = fk::make_fastdiv(cps);
+    a.out = c.out ? c.out + b0 * c.out_bs : nullptr;
+    a.out_bs = c.out_bs;
+}
+
+int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, uint8_t* data,
+                          size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                          int32_t* status, int* err, uint8_t* out, size_t out_bs, uint32_t out_slots,
+                          size_t pss) {
+    if (pss == 0) pss = ss;
+    if ((ss | pss) >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernels take 32-bit shard strides
+    const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
+    const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
+    const uint32_t cps = chunks_of(len);
+    const fk::PlanLayout lay_block = fk::plan_layout(k, maxe), lay_sorted = fk::plan_layout(k, maxe, true);
+    // Three forms:
+    //  * direct (fec_recover.hip): no plan kernel; single-erasure tables of the code, for calls
+    //    where no block can need more (one output slot per block, or m = 1). Small codes (RS(2,3),
+    //    RS(8,12)) and RS(16,24) / RS(20,30) (RS(20,30) single erasure +15 % over plan + rebuild,
+    //    r03h);
+    //  * shards of 32+ chunks: sorted plans (fec_plan.hip), then the wave-form rebuild
+    //    (fec_rebuild.hip for RS(16,24) / RS(20,30) with 64+ chunks, else fec_decode.hip);
+    //  * short shards: plans in block order, then the workgroup-tile rebuild.
+    //  * routed (in-place calls of RS(8,12)): a classify pass reduces the masks to one word; the
+    //    sorted plans run only if some block has two or more erased data shards, and one kernel
+    //    runs the direct body or the wave rebuild by that word (fec_recover.hip).
+    const bool single_slot = out && out_slots == 1;
+    const bool direct = code->d_single_coef && fk::direct_recon_applies(k, m, cps, single_slot);
+    const bool wave = !direct && fk::wave_recon_applies(cps, k, maxe, lay_sorted.stride);
+    const bool routed = wave && !out && code->d_single_coef && !fk::rebuild_k_applies(k, maxe, cps) &&
+                        fk::routed_recon_applies(k, m, cps, maxe, lay_sorted.stride);
+    const fk::PlanLayout lay = wave ? lay_sorted : lay_block;
+    const size_t per_launch = blocks_per_launch(nblocks, cps, direct ? 0 : lay.stride);
+    if (!direct) {
+        const int rc = grow_plans(ctx, per_launch * lay.stride);
+        if (rc) return rc;
+    }
+    if (routed) {
+        const int rc = grow_wflags(ctx, 1);
+        if (rc) return rc;
+    }
+    const uint32_t G = fk::pick_tile_blocks(cps, k, maxe, lay);
+    const ReconCall call{data, dbs, parity, pbs, ss, pss, masks, status, err, out, out_bs, out_slots};
+    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+        fk::PlanArgs p{};
+        fk::ReconArgs a{};
+        fill_recon_slice(p, a, ctx, code, call, len, cps, maxe, lay, G, b0, nb);
+        a.sorted = wave ? 1u : 0u;
+        if (direct || routed) {
+            a.masks = p.masks;
+            a.status = p.status;
+            a.err = p.err;
+            a.prows = p.prows;
+            a.m = m;
+            a.max_out = p.max_out;
+            a.single = code->d_single;
+            a.single_coef = code->d_single_coef;
+            a.single_coef_host = code->single_coef.data();
+            a.sp = fk::decode_store_policy(fk::g_tune.dst_pol, {data, dbs, ss, k}, {parity, pbs, pss, m},
+                                           {out, out_bs, ss, out_slots}, len, nblocks);
+        }
+        if (direct) {
+            HIP_TRY(fk::launch_rs_recover_direct(a, ctx->stream));
+        } else if (routed) {
+            a.route = p.route = ctx->work->d_wflags;
+            HIP_TRY(fk::launch_rs_route_classify(a, ctx->work->d_wflags, ctx->stream));
+            HIP_TRY(fk::launch_rs_plan_sorted(p, ctx->stream));
+            HIP_TRY(fk::launch_rs_reconstruct_routed(a, ctx->stream));
+        } else if (wave) {
+            HIP_TRY(fk::launch_rs_plan_sorted(p, ctx->stream));
+            if (fk::rebuild_k_applies(k, maxe, cps)) HIP_TRY(fk::launch_rs_rebuild_k(a, ctx->stream));
+            else HIP_TRY(fk::launch_rs_reconstruct_wave(a, ctx->stream));
+        } else {
+            HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
+            HIP_TRY(fk::launch_rs_reconstruct(a, (int)std::max<uint32_t>(1, a.ntiles), ctx->stream));
+        }
+        return FEC_OK;
+    });
+}
+
+// The wide tile (fec_wide.hip rs_rebuild_wide_kernel) over a batch: records of `rows` output rows per
+// block, cut into launches under kPlanBytes of records and kMaxItems items; for each, plan(b0, nb,
+// lay) writes the launch's records into the stream's workspace, then the tile rebuilds from them:
+// `some` false into out (if set) or the data region, true into the data and the parity region.
+template <class Plan>
+static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, size_t len, size_t nblocks, uint8_t* data,
+                            size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, uint8_t* out, size_t out_bs,
+                            bool some, Plan plan) {
+    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
+    const uint32_t cps = chunks_of(len);
+    const fk::WideLayout lay = fk::wide_layout(k, rows);
+    const size_t per_launch = blocks_per_launch(nblocks, cps, lay.stride);
+    const int rc = grow_plans(ctx, per_launch * lay.stride);
+    if (rc) return rc;
+    uint32_t G, C, TK;
+    fk::wide_tile_shape(cps, k, &G, &C, &TK);
+    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+        fk::WideReconArgs a{};
+        a.data = data + b0 * dbs;
+        a.parity = parity + b0 * pbs;
+        a.dbs = dbs;
+        a.pbs = pbs;
+        a.ss = (uint32_t)ss;
+        a.plans = ctx->work->d_plans;
+        a.lay = lay;
+        a.k = k;
+        a.len = (uint32_t)len;
+        a.cps = cps;
+        a.nblocks = (uint32_t)nb;
+        a.g = G;
+        a.c = C;
+        a.tk = TK;
+        a.nctiles = (cps + C - 1) / C;
+        a.ntiles = (uint32_t)((nb + G - 1) / G) * a.nctiles;
+        a.div_c = fk::make_fastdiv(C);
+        a.div_nct = fk::make_fastdiv(a.nctiles);
+        a.out = out ? out + b0 * out_bs : nullptr;
+        a.out_bs = out_bs;
+        HIP_TRY(plan(b0, nb, lay));
+        HIP_TRY(fk::launch_rs_rebuild_wide(a, some, ctx->stream));
+        return FEC_OK;
+    });
+}
+
+// Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
+// up to 256 shards.
+int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
+                               size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
+                               const uint32_t* masks, size_t mask_words, int32_t* status, int* err,
+                               uint8_t* out, size_t out_bs, uint32_t out_slots) {
+    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
+    if (out) rows = std::min(rows, out_slots);
+    return rs_rebuild_tiles(ctx, k, rows, len, nblocks, data, dbs, parity, pbs, ss, out, out_bs, false,
+                            [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                fk::WidePlanArgs p{};
+                                p.masks = masks + b0 * mask_words;
+                                p.mask_words = (uint32_t)mask_words;
+                                p.plans = ctx->work->d_plans;
+                                p.status = status ? status + b0 : nullptr;
+                                p.err = err;
+                                p.k = k;
+                                p.n = k + m;
+                                p.nblocks = (uint32_t)nb;
+                                p.rows = rows;
+                                p.max_out = out ? out_slots : 0;
+                                p.lay = lay;
+                                p.div_k = fk::make_fastdiv(k);
+                                return fk::launch_rs_plan_wide(p, ctx->stream);
+                            });
+}
+
+// Verify (fec_verify.hip): statuses pre-set to 1 and the count to 0 on the stream, then the encode's
+// launches (cut under kMaxItems items, parity rows in passes of 16) with the stored parity folded
+// in: a pass clears the word of a block it finds bad and counts it if no earlier pass had.
+int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                     const uint8_t* parity, size_t pbs, size_t ss, int32_t* status, uint32_t* count) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 1, nblocks, ctx->stream));
+    if (count) HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::VerifyArgs a{};
+            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
+            a.par = parity + b0 * pbs + (size_t)r0 * ss;
+            a.par_bs = pbs;
+            a.len = (uint32_t)len;
+            a.cps = cps;
+            a.total = (uint32_t)(nb * cps);
+            a.div_cps = fk::make_fastdiv(cps);
+            a.status = status + b0;
+            a.count = count;
+            HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
+        }
+        return FEC_OK;
+    });
+}
+
+// Update and encode-idx (fec_update.hip; UpdateCall, fec_ctx.hpp, holds a call's regions and masks).
+// The arguments of one launch: blocks [b0, b0 + nb) of the call, the pass of up to 16 parity rows
+// from r0. No device work (fec__selftest_update_slices calls it without one).
+static void fill_update_launch(fk::UpdateArgs& a, const Code* code, int r0, size_t b0, size_t nb, size_t len,
+                               const UpdateCall& u) {
+    const uint32_t cps = chunks_of(len);
+    fill_row_pass(a, code, r0, u.in + b0 * u.in_bs, u.in_bs, u.ss);
+    a.old = u.old ? u.old + b0 * u.old_bs : nullptr;
+    a.old_bs = u.old_bs;
+    a.par = u.parity + b0 * u.pbs + (size_t)r0 * u.ss;
+    a.par_bs = u.pbs;
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.total = (uint32_t)(nb * cps);
+    a.nblocks = (uint32_t)nb;
+    a.div_cps = fk::make_fastdiv(cps);
+    a.masks = u.masks + b0 * u.mask_words;
+    a.mask_words = (uint32_t)u.mask_words;
+}
+
+// emit(args) for every launch of a call: the encode's cut under kMaxItems items, parity rows in
+// passes of 16 (each pass reads the masked columns again), until one fails.
+template <class F>
+static int update_launches(const Code* code, size_t len, size_t nblocks, const UpdateCall& u, F emit) {
+    return for_slices(nblocks, blocks_per_launch(nblocks, chunks_of(len)), [&](size_t b0, size_t nb) -> int {
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::UpdateArgs a{};
+            fill_update_launch(a, code, r0, b0, nb, len, u);
+            const int rc = emit(a);
+            if (rc) return rc;
+        }
+        return FEC_OK;
+    });
+}
+
+int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const UpdateCall& u) {
+    return update_launches(code, len, nblocks, u, [&](const fk::UpdateArgs& a) -> int {
+        HIP_TRY(fk::launch_rs_update(a, flat_grid(a.total), ctx->stream));
+        return FEC_OK;
+    });
+}
+
+// Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
+// the wide tile, storing into both regions.
+int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
+                               size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                               const uint32_t* want, int32_t* status, int* err) {
+    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    return rs_rebuild_tiles(ctx, k, fk::some_rows(m), len, nblocks, data, dbs, parity, pbs, ss, nullptr, 0, true,
+                            [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                fk::SomePlanArgs p{};
+                                p.masks = masks + b0;
+                                p.want = want ? want + b0 : nullptr;
+                                p.plans = ctx->work->d_plans;
+                                p.status = status ? status + b0 : nullptr;
+                                p.err = err;
+                                p.k = k;
+                                p.n = k + m;
+                                p.nblocks = (uint32_t)nb;
+                                p.lay = lay;
+                                return fk::launch_rs_plan_some(p, ctx->stream);
+                            });
+}
+
+// Ragged batches (fec_ragged.hip): block b's shards are lens[b] bytes long, at most max_len. Cut
+// into launches as the uniform calls are, with cps_max = the chunks of a shard of max_len bytes.
+static uint32_t ragged_encode_blocks(uint32_t cps_max) {
+    const int forced = fk::g_tune.rag_g;
+    // a tile of full-length blocks fills one window (kRagRounds rounds)
+    const uint32_t want = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps_max);
+    return fk::rag_clamp_blocks(want, cps_max);
+}
+
+int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, const uint8_t* data,
+                            size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* lens,
+                            int32_t* status, int* err) {
+    const uint32_t cps = chunks_of(max_len);
+    const uint32_t G = ragged_encode_blocks(cps);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::RagEncodeArgs a{};
+            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
+            a.out = parity + b0 * pbs + (size_t)r0 * ss;
+            a.out_bs = pbs;
+            a.max_len = (uint32_t)max_len;
+            a.nblocks = (uint32_t)nb;
+            a.g = G;
+            a.nwin = fk::rag_windows(G, cps);
+            a.lens = lens + b0;
+            a.status = status ? status + b0 : nullptr;
+            a.err = err;
+            a.report = r0 == 0;
+            HIP_TRY(fk::launch_rs_encode_ragged(a, ctx->stream));
+        }
+        return FEC_OK;
+    });
+}
+
+// Plans in block order by rs_plan_kernel (they do not depend on the length), then the ragged tile
+// rebuild, which also overrides the status of oversize blocks.
+int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, uint8_t* data,
+                                 size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
+                                 const uint32_t* masks, const uint32_t* lens, int32_t* status, int* err,
+                                 uint8_t* out, size_t out_bs, uint32_t out_slots) {
+    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild takes 32-bit shard strides
+    const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
+    const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
+    const uint32_t cps = chunks_of(max_len);
+    const fk::PlanLayout lay = fk::plan_layout(k, maxe);
+    const size_t per_launch = blocks_per_launch(nblocks, cps, lay.stride);
+    const int rc = grow_plans(ctx, per_launch * lay.stride);
+    if (rc) return rc;
+    // rows a block can need: the plan kernel gives a block with more erasures than slots no rows
+    const uint32_t rows = out ? std::min(maxe, out_slots) : maxe;
+    // Blocks per tile: as the encode's, so that a tile of full-length blocks fills one window, within
+    // what LDS holds. (pick_tile_blocks, the uniform tile form's choice, looks for the fewest blocks
+    // that fill the lanes of a full-length tile: RS(20,30) 3. A ragged tile has fewer items than
+    // that, and its fixed cost, two barriers for the prefix and one for the tables, is paid per
+    // tile. Measured, the rebuild is indifferent between the two within the run-to-run spread; the
+    // encode is 30-42 % slower at 3 blocks per tile: DESIGN.md 4b.)
+    const int forced = fk::g_tune.rag_g;
+    uint32_t G = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps);
+    G = fk::rag_clamp_blocks(std::min(G, fk::rag_recon_max_blocks(k, rows, lay)), cps);
+    const ReconCall call{data, dbs, parity, pbs, ss, ss, masks, status, err, out, out_bs, out_slots};
+    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+        fk::PlanArgs p{};
+        fk::RagReconArgs ra{};
+        fill_recon_slice(p, ra.r, ctx, code, call, max_len, cps, maxe, lay, G, b0, nb);
+        ra.r.status = p.status;
+        ra.r.err = err;
+        ra.lens = lens + b0;
+        ra.max_len = (uint32_t)max_len;
+        ra.nwin = fk::rag_windows(G, cps);
+        ra.rows = rows;
+        HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
+        HIP_TRY(fk::launch_rs_reconstruct_ragged(ra, ctx->stream));
+        return FEC_OK;
+    });
+}
+
+// The XOR calls' launch arguments for blocks [b0, b0 + nb): the encode's, and the in-place
+// reconstruct's (data rebuilt where it lies, parity read).
+static fk::XorArgs xor_slice(int k, size_t len, uint32_t cps, const uint8_t* in, size_t in_bs, uint8_t* out,
+                             size_t out_bs, size_t ss, size_t b0, size_t nb) {
+    fk::XorArgs a{};
+    a.in = in + b0 * in_bs;
+    a.out = out + b0 * out_bs;
+    a.in_bs = in_bs;
+    a.out_bs = out_bs;
+    a.ss = ss;
+    a.k = (uint32_t)k;
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.total = (uint32_t)(nb * cps);
+    a.div_cps = fk::make_fastdiv(cps);
+    return a;
+}
+
+int xor_encode_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                      uint8_t* parity, size_t pbs, size_t ss) {
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        const fk::XorArgs a = xor_slice(k, len, cps, data, dbs, parity, pbs, ss, b0, nb);
+        HIP_TRY(fk::launch_xor_encode(a, flat_grid(a.total), ctx->stream));
+        return FEC_OK;
+    });
+}
+
+int xor_reconstruct_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                           const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                           int32_t* status, int* err) {
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        fk::XorArgs a = xor_slice(k, len, cps, data, dbs, data, dbs, ss, b0, nb);
+        a.parity = parity + b0 * pbs;
+        a.par_bs = pbs;
+        a.masks = masks + b0;
+        a.status = status ? status + b0 : nullptr;
+        a.err = err;
+        a.nblocks = (uint32_t)nb;
+        HIP_TRY(fk::launch_xor_reconstruct(a, flat_grid(a.total), ctx->stream));
+        return FEC_OK;
+    });
+}
+
+extern "C" {
+
+// Internal self-test (not part of the public ABI, no device needed): the launches of an update call
+// that the launch limit cuts. k = 5, m = 20, 70 000-byte shards (4375 chunks), one block more than
+// kMaxItems / 4375: two launches (490 853 blocks, then one) of two row passes each (16 rows, then
+// 4). Every launch's three region bases, mask pointer, item count, row count and table base are
+// compared with values worked out here from the call's strides, without the functions under test.
+// 0 on success, else 10 * (launch index + 1) + the failing field.
+int fec__selftest_update_slices(void) {
+    const int k = 5, m = 20;
+    const size_t L = 70000, cps = 4375, per = 490853, B = per + 1, W = 3;
+    if (per != (size_t)(kMaxItems / cps)) return 1;
+    const size_t ss = 70016, in_bs = k * ss + 48, old_bs = k * ss + 16, pbs = m * ss + 32;
+    const uintptr_t in0 = uintptr_t(1) << 40, old0 = uintptr_t(2) << 40, par0 = uintptr_t(3) << 40,
+                    mask0 = uintptr_t(4) << 40, tab0 = uintptr_t(5) << 40;
+    Code code;
+    code.k = k;
+    code.m = m;
+    code.d_tabs = (uint32_t*)tab0;
+    const UpdateCall u{(const uint8_t*)in0, in_bs, (const uint8_t*)old0, old_bs, (uint8_t*)par0, pbs, ss,
+                       (const uint32_t*)mask0, W};
+    std::vector<fk::UpdateArgs> got;
+    const int rc = update_launches(&code, L, B, u, [&](const fk::UpdateArgs& a) -> int {
+        got.push_back(a);
+        return FEC_OK;
+    });
+    code.d_tabs = nullptr;
+    if (rc != FEC_OK || got.size() != 4) return 2;
+    for (size_t i = 0; i < 4; ++i) {
+        const fk::UpdateArgs& a = got[i];
+        const int fail = 10 * ((int)i + 1);
+        const size_t b0 = (i / 2) * per, nb = i / 2 ? 1 : per, r0 = (i % 2) * 16;
+        if ((uintptr_t)a.in != in0 + b0 * in_bs || a.in_bs != in_bs) return fail + 1;
+        if ((uintptr_t)a.old != old0 + b0 * old_bs || a.old_bs != old_bs) return fail + 2;
+        if ((uintptr_t)a.par != par0 + b0 * pbs + r0 * ss || a.par_bs != pbs || a.ss != ss) return fail + 3;
+        if ((uintptr_t)a.masks != mask0 + b0 * W * 4 || a.mask_words != W) return fail + 4;
+        if (a.total != nb * cps || a.nblocks != nb || a.cps != cps || a.len != L) return fail + 5;
+        if (a.k != (uint32_t)k || a.m != (i % 2 ? 4u : 16u)) return fail + 6;
+        if ((uintptr_t)a.tabs != tab0 + r0 * k * 8 * 4) return fail + 7;
+        if (a.div_cps.d != cps) return fail + 8;
+    }
+    // encode-idx: no old region in any launch
+    UpdateCall e = u;
+    e.old = nullptr;
+    fk::UpdateArgs a{};
+    code.d_tabs = (uint32_t*)tab0;
+    fill_update_launch(a, &code, 16, per, 1, L, e);
+    code.d_tabs = nullptr;
+    if (a.old != nullptr || (uintptr_t)a.in != in0 + per * in_bs) return 3;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,189 @@
+// fec_ctx.hpp — what the host translation units of the C ABI share (internal): the per-device
+// context and its limits (fec_capi.cpp owns its lifecycle and the code cache), the device-memory
+// cores (fec_cores.cpp) and the host-resident drivers (fec_host.cpp) that the entry points call.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <initializer_list>
+#include <map>
+#include <utility>
+#include <vector>
+
+#include "../../include/fec_hip.h"
+
+#pragma GCC visibility push(hidden)
+
+struct Code {
+    int k = 0, m = 0;
+    std::vector<uint8_t> matrix;   // n x k
+    uint8_t* d_prows = nullptr;    // m x k
+    uint32_t* d_tabs = nullptr;    // m x k PermTabs
+    uint32_t* d_dytabs = nullptr;  // dyadic codes: leaf PermTabs of the split-recursive encode
+    uint32_t* d_single = nullptr;  // single-erasure decode tables (fk::direct_table_words), when small
+    uint32_t* d_single_coef = nullptr;   // their coefficient bytes, (k*m) rows of ceil(k/4) dwords
+    std::vector<uint32_t> single_coef;   // host copy
+    uint8_t* d_dall = nullptr;     // n bytes: sum_{t != s} log(s ^ t) mod 255 (sorted plans)
+};
+
+// Bytes of staged shards per FEC_HOST chunk (x2 buffers, in and out).
+constexpr size_t kStageBytes = size_t(128) << 20;
+// Upper bound on decode plan workspace.
+constexpr size_t kPlanBytes = size_t(256) << 20;
+// nblocks * chunks-per-shard must stay below 2^31 per launch (32-bit item ids).
+constexpr uint64_t kMaxItems = uint64_t(1) << 31;
+
+// Device scratch of the kernels enqueued on one stream: decode plan records. Each stream the ctx
+// launches on (its own / the caller's, and one per host-path staging set) has its own, so
+// launches that overlap on different streams never share one (nor free one the other stream
+// still reads).
+struct Work {
+    uint8_t* d_plans = nullptr;
+    size_t plans_cap = 0;
+    uint32_t* d_wflags = nullptr;   // routed in-place decode: the classify pass's route word
+    size_t wflags_cap = 0;
+    void release() {
+        if (d_plans) (void)hipFree(d_plans);
+        if (d_wflags) (void)hipFree(d_wflags);
+        *this = Work{};
+    }
+};
+
+// One staging set of the host-resident path: pinned host and device buffers for one chunk of
+// blocks, and the events that carry that chunk through the pipeline's streams (HostPipe).
+struct HostSet {
+    uint8_t* h_in = nullptr;
+    uint8_t* h_out = nullptr;
+    uint8_t* d_in = nullptr;
+    uint8_t* d_out = nullptr;
+    uint32_t* h_masks = nullptr;
+    uint32_t* d_masks = nullptr;
+    int32_t* h_status = nullptr;
+    int32_t* d_status = nullptr;
+    uint8_t* d_raw_in = nullptr;    // FEC_HOST_PINNED: the caller's span, copied linearly (fec_pack.hip)
+    uint8_t* d_raw_out = nullptr;   // FEC_HOST_PINNED: the packed image of the outputs, copied down linearly
+    size_t in_cap = 0, out_cap = 0, blk_cap = 0, raw_in_cap = 0, raw_out_cap = 0;
+    hipEvent_t up_done = nullptr;     // its H2D copies have landed
+    hipEvent_t k_done = nullptr;      // its kernels are done (the device inputs are free)
+    hipEvent_t down_done = nullptr;   // its D2H copies have landed (the set is free)
+};
+
+// The host-resident pipeline. Chunk c of a call uses set c % kHostSets and moves through three
+// streams in order: H2D copies on `up`, kernels on `comp`, D2H copies on `down`, ordered by the
+// set's events alone. PCIe's two directions and the kernels of different chunks therefore overlap,
+// and the up direction (the larger one on every path) never waits for the host: the host blocks only
+// to reuse a set, on its chunk kHostSets back, and at the end of a call. Measured on one MI355X
+// (tools/pcie_duplex_probe.hip, profiles/r04/pcie_duplex_probe_r04b.log): H2D 57.6 GB/s, D2H 57.0,
+// both at once 48.6 each way; this shape with 64 MiB chunks moved 53.8 GB/s up.
+constexpr int kHostSets = 3;
+struct HostPipe {
+    hipStream_t up = nullptr, comp = nullptr, down = nullptr;
+    Work w;   // scratch of the kernels on comp
+    HostSet set[kHostSets];
+};
+
+struct fec_ctx {
+    int device = 0;
+    hipStream_t own = nullptr;
+    hipStream_t stream = nullptr;
+    std::map<std::pair<int, int>, Code> codes;
+    Work main;               // scratch of the kernels on `own` / the caller's stream
+    Work* work = &main;      // scratch of the kernels on `stream` (on_stream switches both)
+    int* d_err = nullptr;    // [0] sticky device-path error, [1] host-path error
+    uint8_t* h_stage = nullptr;
+    uint8_t* d_stage = nullptr;
+    size_t stage_cap = 0;
+    uint32_t* d_masks = nullptr;
+    int32_t* d_status = nullptr;
+    size_t masks_cap = 0;
+    HostPipe pipe;           // host-resident path (FEC_HOST / FEC_HOST_PINNED)
+    hipEvent_t handoff = nullptr;   // orders a newly set stream after the previous one
+};
+
+#define HIP_TRY(expr)                      \
+    do {                                   \
+        if ((expr) != hipSuccess) {        \
+            (void)hipGetLastError();       \
+            return FEC_ERR_HIP;            \
+        }                                  \
+    } while (0)
+
+inline size_t round16(size_t x) { return (x + 15) & ~size_t(15); }
+
+// ---------------------------------------------------------------- fec_capi.cpp
+int select_device(fec_ctx* ctx);
+int get_code(fec_ctx* ctx, int k, int m, Code** out);
+// Grow the buffers that share capacity *cap (counted in units of `unit` bytes) to hold n units:
+// pinned host memory where `pinned`, else device memory. No stream may still use the old ones.
+struct GrowBuf {
+    void** p;
+    bool pinned;
+};
+int grow_bufs(size_t* cap, size_t n, size_t unit, std::initializer_list<GrowBuf> bufs);
+// The ctx's own buffers (of ctx->work: plans, wflags), grown once ctx->stream has drained.
+int grow_plans(fec_ctx* ctx, size_t bytes);
+int grow_wflags(fec_ctx* ctx, size_t n);
+int grow_stage(fec_ctx* ctx, size_t bytes);
+int grow_masks(fec_ctx* ctx, size_t n);
+
+// ---------------------------------------------------------------- fec_cores.cpp: device-memory cores
+// Each enqueues one call's launches on ctx->stream, with ctx->work as their scratch.
+int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                     uint8_t* parity, size_t pbs, size_t ss);
+int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                          const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, int32_t* status,
+                          int* err, uint8_t* out = nullptr, size_t out_bs = 0, uint32_t out_slots = 0,
+                          size_t pss = 0);
+int rs_reconstruct_wide_device(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                               const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                               size_t mask_words, int32_t* status, int* err, uint8_t* out = nullptr,
+                               size_t out_bs = 0, uint32_t out_slots = 0);
+int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                     const uint8_t* parity, size_t pbs, size_t ss, int32_t* status, uint32_t* count);
+// Update and encode-idx (fec_update.hip): the regions and masks of one call. `in` is the data folded
+// in (update: the new version), `old` the old version (encode-idx: null).
+struct UpdateCall {
+    const uint8_t* in;
+    size_t in_bs;
+    const uint8_t* old;
+    size_t old_bs;
+    uint8_t* parity;
+    size_t pbs, ss;
+    const uint32_t* masks;
+    size_t mask_words;
+};
+int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const UpdateCall& u);
+int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                               uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, const uint32_t* want,
+                               int32_t* status, int* err);
+int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, const uint8_t* data,
+                            size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* lens,
+                            int32_t* status, int* err);
+int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, uint8_t* data,
+                                 size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                                 const uint32_t* lens, int32_t* status, int* err, uint8_t* out = nullptr,
+                                 size_t out_bs = 0, uint32_t out_slots = 0);
+int xor_encode_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                      uint8_t* parity, size_t pbs, size_t ss);
+int xor_reconstruct_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                           const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, int32_t* status,
+                           int* err);
+
+// ---------------------------------------------------------------- fec_host.cpp: host-resident path
+// Encode (RS when code != nullptr, else XOR(k, 1)): host data -> host parity.
+int host_encode(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
+                uint8_t* parity, size_t pbs, size_t ss, bool pinned);
+int host_reconstruct_rs(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nblocks, uint8_t* data,
+                        size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                        int32_t* block_status, bool pinned);
+int host_reconstruct_xor(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                         const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+                         int32_t* block_status);
+int host_reconstruct_wide(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
+                          const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, size_t mask_words,
+                          int32_t* block_status);
+// Free every buffer of the set and forget it (pointers null, capacities 0), whatever a free
+// returns; the first failure, or hipSuccess. The set's events stay.
+hipError_t host_set_free(HostSet& s);
+
+#pragma GCC visibility pop

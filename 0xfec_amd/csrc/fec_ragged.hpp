@@ -1,5 +1,5 @@
 // fec_ragged.hpp — ragged batches (a shard length per block): the item arithmetic shared by the
-// kernels of fec_ragged.hip and the host self-test (fec__selftest_ragged_tiles, fec_capi.cpp), and
+// kernels of fec_ragged.hip and the host self-test (fec__selftest_ragged_tiles, fec_selftest.cpp), and
 // the launch interface of fec_ragged.hip.
 //
 // A workgroup takes one window of one tile. A tile is G consecutive blocks; its items are the

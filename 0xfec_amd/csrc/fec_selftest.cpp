@@ -1,0 +1,320 @@
+// fec_selftest.cpp — device-free self-tests of the host-visible arithmetic the kernels share with
+// the host (the fk:: / gf:: / rs:: functions of the headers below). The self-tests of file-local
+// code stand beside it: fec__selftest_update_slices in fec_cores.cpp, fec__selftest_copypool in
+// fec_host.cpp.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/fec_hip.h"
+#include "fec_kernels.hpp"
+#include "fec_ragged.hpp"
+#include "fec_some.hpp"
+#include "fec_wide.hpp"
+#include "gf256.h"
+#include "rs_matrix.hpp"
+
+extern "C" {
+
+// Internal self-test (not part of the public ABI, no device needed): the lane-arithmetic PermTab
+// builder the kernels use equals the byte-wise one for every coefficient. 0 on success, else
+// 1 + the first failing coefficient.
+int fec__selftest_permtab(void) {
+    for (uint32_t c = 0; c < 256; ++c) {
+        const gf::PermTab a = gf::make_permtab((uint8_t)c), b = gf::make_permtab_fast(c);
+        if (a.t0lo != b.t0lo || a.t0hi != b.t0hi || a.t1lo != b.t1lo || a.t1hi != b.t1hi || a.t2 != b.t2)
+            return 1 + (int)c;
+    }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the store policy of a call
+// follows the hulls of its shard regions (fec_kernels.hpp regions_apart) for block-major and
+// shard-major layouts. Addresses are only compared, never dereferenced. 0 on success, else
+// 1 + the index of the first failing row.
+int fec__selftest_store_policy(void) {
+    const uint64_t S = 1216, L = 1202, B = 67, k = 8, m = 4;
+    const uintptr_t base = 0x10000000;
+    auto at = [&](uint64_t off) { return (const void*)(base + off); };
+    struct Row {
+        int st_pol;
+        fk::ShardRegion data, parity;
+        uint64_t nblocks;
+        uint32_t want;
+    };
+    const Row rows[] = {
+        // split, block-major [B][k][S] + [B][m][S]: apart (parity above data, and below it)
+        {1, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, B, 1u},
+        {1, {at(B * m * S), k * S, S, k}, {at(0), m * S, S, m}, B, 1u},
+        // (those two touch); one 16-byte chunk into each other
+        {1, {at(0), k * S, S, k}, {at(B * k * S - 16), m * S, S, m}, B, 0u},
+        // interleaved [B][k+m][S]: parity slots among the data
+        {1, {at(0), (k + m) * S, S, k}, {at(k * S), (k + m) * S, S, m}, B, 0u},
+        // one block of it: its parity lies past its data
+        {1, {at(0), (k + m) * S, S, k}, {at(k * S), (k + m) * S, S, m}, 1, 1u},
+        // shard-major [k+m][B][S] in one region: parity rows after the last data row
+        {1, {at(0), S, B * S, k}, {at(k * B * S), S, B * S, m}, B, 1u},
+        // shard-major, parity rows in the gaps between the data rows
+        {1, {at(0), S, 2 * B * S, k}, {at(B * S), S, 2 * B * S, m}, B, 0u},
+        // shard-major data, block-major parity inside the data's second row
+        {1, {at(0), S, B * S, k}, {at(B * S), m * S, S, m}, 8, 0u},
+        // no blocks: nothing to claim
+        {1, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, 0, 0u},
+        // knob values: 0 nt whatever the layout, 2 sc1 whatever the layout
+        {0, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, B, 0u},
+        {2, {at(0), (k + m) * S, S, k}, {at(k * S), (k + m) * S, S, m}, B, 1u},
+        {2, {at(0), k * S, S, k}, {at(B * k * S), m * S, S, m}, 0, 1u},
+    };
+    int i = 0;
+    for (const Row& r : rows) {
+        ++i;
+        if (fk::encode_store_policy(r.st_pol, r.data, r.parity, L, r.nblocks) != r.want) return i;
+        // symmetric in its two regions
+        if (fk::encode_store_policy(r.st_pol, r.parity, r.data, L, r.nblocks) != r.want) return i;
+    }
+    // decode: nt sc1 (3) only into an out region apart from both the data and the parity read
+    const fk::ShardRegion d{at(0), S, B * S, k}, p{at(k * B * S), S, B * S, m};
+    const fk::ShardRegion out_far{at((k + m) * B * S), S, B * S, m}, out_in_parity{at((k + 1) * B * S), S, B * S, 1};
+    const fk::ShardRegion out_rows_over_data{at(B * S - 16 * S), 16 * S, S, m}, none{nullptr, 0, 0, 0};
+    if (fk::decode_store_policy(3, d, p, out_far, L, B) != 3u) return 101;
+    if (fk::decode_store_policy(3, d, p, out_in_parity, L, B) != 0u) return 102;
+    if (fk::decode_store_policy(3, d, p, out_rows_over_data, L, B) != 0u) return 103;
+    if (fk::decode_store_policy(3, d, p, none, L, B) != 0u) return 104;       // in place
+    if (fk::decode_store_policy(0, d, p, out_far, L, B) != 0u) return 105;    // knob: nt
+    if (fk::decode_store_policy(3, d, p, out_far, L, 0) != 0u) return 106;
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the records some_plan_record
+// builds (fec_some.hpp, the function rs_plan_some_kernel runs) against the systematic matrix. For
+// 64 seeded recoverable masks per code, plus all parity lost and, where m >= k, exactly k present
+// with all of them parity: want = every shard; the inputs are the first k present shards, the
+// outputs every missing shard, ascending, and row r equals M[O[r]] * inverse(rows S of M), parity
+// rows included. Then the same mask with a seeded want mask: the outputs are the wanted missing
+// shards with the rows they had, a want mask naming nothing missing gives an empty record, and a
+// mask with k - 1 present gives too-few exactly when something is to rebuild. 0 on success, else
+// 1000 * (code index + 1) + mask index + 1.
+int fec__selftest_some_plan(void) {
+    static const int shapes[][2] = {{8, 4}, {2, 1}, {20, 10}, {10, 22}, {1, 31}, {31, 1}};
+    uint8_t ex768[768];
+    for (uint32_t i = 0; i < 768; ++i) ex768[i] = fk::wide_exp768(i);
+    const uint8_t* lg = gf::kTables.log;
+    uint64_t seed = 0xD1B54A32D192ED03ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix((int)k, (int)n);
+        if (M.empty()) return 1000 * si;
+        const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
+        const uint32_t all = fk::low_mask(n);
+        // stray bits at and above n are set in both masks throughout: they are ignored
+        const uint32_t stray = ~all;
+        std::vector<uint8_t> rec(lay.stride), rec2(lay.stride);
+        const int cases = 64 + 1 + (m >= k ? 1 : 0);
+        for (int ci = 0; ci < cases; ++ci) {
+            const int fail = 1000 * si + ci + 1;
+            uint32_t pres = all;
+            if (ci == 64) {
+                pres = fk::low_mask(k);                    // all parity lost
+            } else if (ci == 65) {
+                pres = (fk::low_mask(k) << k) & all;       // exactly k present, all of them parity
+            } else {
+                for (uint32_t lose = rnd() % (m + 1); lose > 0;) {
+                    const uint32_t i = rnd() % n;
+                    if ((pres >> i) & 1u) {
+                        pres &= ~(1u << i);
+                        --lose;
+                    }
+                }
+            }
+            std::vector<uint8_t> S, O;
+            for (uint32_t i = 0; i < n && S.size() < k; ++i)
+                if ((pres >> i) & 1u) S.push_back((uint8_t)i);
+            for (uint32_t i = 0; i < n; ++i)
+                if (!((pres >> i) & 1u)) O.push_back((uint8_t)i);
+            std::fill(rec.begin(), rec.end(), 0xEE);
+            if (fk::some_plan_record(rec.data(), lay, pres | stray, 0xFFFFFFFFu, k, n, ex768, lg) != 0) return fail;
+            if (rec[lay.nout_off] != O.size()) return fail;
+            if (O.empty()) continue;
+            if (memcmp(&rec[lay.in_off], S.data(), k) || memcmp(&rec[lay.out_off], O.data(), O.size())) return fail;
+            std::vector<uint8_t> inv((size_t)k * k);
+            for (uint32_t p = 0; p < k; ++p) memcpy(&inv[(size_t)p * k], &M[(size_t)S[p] * k], k);
+            if (!rs::invert((int)k, inv.data())) return fail;
+            for (size_t r = 0; r < O.size(); ++r)
+                for (uint32_t p = 0; p < k; ++p) {
+                    uint8_t c = 0;   // (M[o] * inv)[p]
+                    for (uint32_t t = 0; t < k; ++t) c ^= gf::mul(M[(size_t)O[r] * k + t], inv[(size_t)t * k + p]);
+                    if (rec[lay.coef_off + r * k + p] != c) return fail;
+                }
+            // a want mask: only the wanted missing shards, each with the row it had
+            const uint32_t want = rnd() & all;
+            std::fill(rec2.begin(), rec2.end(), 0xEE);
+            if (fk::some_plan_record(rec2.data(), lay, pres, want | stray, k, n, ex768, lg) != 0) return fail;
+            uint32_t r2 = 0;
+            for (size_t r = 0; r < O.size(); ++r) {
+                if (!((want >> O[r]) & 1u)) continue;
+                if (rec2[lay.out_off + r2] != O[r] ||
+                    memcmp(&rec2[lay.coef_off + r2 * k], &rec[lay.coef_off + r * k], k))
+                    return fail;
+                ++r2;
+            }
+            if (rec2[lay.nout_off] != r2) return fail;
+            if (fk::some_plan_record(rec2.data(), lay, pres, pres | stray, k, n, ex768, lg) != 0 || rec2[lay.nout_off])
+                return fail;
+            // k - 1 present: too few exactly when something is to rebuild
+            uint32_t few = 0;
+            for (uint32_t p = 0; p + 1 < k; ++p) few |= 1u << S[p];
+            if (fk::some_plan_record(rec2.data(), lay, few, 0xFFFFFFFFu, k, n, ex768, lg) != FEC_ERR_TOO_FEW_SHARDS ||
+                rec2[lay.nout_off])
+                return fail;
+            if (fk::some_plan_record(rec2.data(), lay, few, few, k, n, ex768, lg) != 0 || rec2[lay.nout_off]) return fail;
+        }
+    }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the item arithmetic of the
+// ragged kernels (fec_ragged.hpp), walked as the kernels walk it. For each row of a table of length
+// vectors and tile sizes, every workgroup's tile and window are taken, its rounds of 256 lanes
+// swept, and each item located in the tile's prefix: the items met, in order, must be exactly the
+// (block, chunk) pairs of the batch in order, chunk below the block's count, each once, none
+// missing; a window past its tile's item count must be empty, and no workgroup may run more than
+// kRagRounds rounds. 0 on success, else 100 * (row + 1) + the failing check.
+int fec__selftest_ragged_tiles(void) {
+    struct Row {
+        std::vector<uint32_t> lens;
+        uint32_t max_len, g;
+    };
+    const uint32_t W = fk::kRagWindow, K16 = (uint32_t)fk::kChunk;
+    std::vector<Row> rows;
+    rows.push_back({std::vector<uint32_t>(40, 0), 1202, 8});                        // all-zero tiles
+    {   // a zero run spanning a tile edge (blocks 5..10 of tiles of 8), an oversize block in it
+        std::vector<uint32_t> l = {1202, 1, 16, 17, 50, 0, 0, 0, 0, 1203, 0, 33, 1202, 0, 15, 1200, 0xFFFFFFFFu, 7};
+        rows.push_back({l, 1202, 8});
+        rows.push_back({l, 1202, 3});
+        rows.push_back({l, 1202, 1});
+        rows.push_back({l, 1202, 256});
+    }
+    rows.push_back({{1202}, 1202, 16});                                             // a single block
+    rows.push_back({{1}, 1202, 1});
+    for (int d = -1; d <= 1; ++d) {   // a tile's sum = a multiple of 256, one less, one more
+        rows.push_back({{16u * 200u, 0, 16u * (uint32_t)(56 + d), 16u * 256u}, 16u * 256u, 4});
+        rows.push_back({{16u * (uint32_t)(256 + d)}, 16u * 300u, 1});
+        rows.push_back({{16u * (W / 2), 16u * (uint32_t)((int)(W / 2) + d)}, 16u * W, 2});   // and of a window
+    }
+    rows.push_back({{70000, 1, 33333}, 70000, 1});                                  // several windows per tile
+    rows.push_back({{70000, 1, 33333}, 70000, 16});
+    rows.push_back({{5, 0, 1u << 30, 17}, 1u << 30, 64});                           // a 2^26-chunk shard
+    int row = 0;
+    for (const Row& r : rows) {
+        const int fail = 100 * ++row;
+        const uint32_t nblocks = (uint32_t)r.lens.size();
+        const uint32_t cps_max = (r.max_len + K16 - 1) / K16;
+        const uint32_t G = fk::rag_clamp_blocks(r.g, cps_max);
+        if (G < 1 || G > fk::kRagMaxTileBlocks || (uint64_t)G * cps_max > fk::kRagMaxTileItems) return fail + 1;
+        const uint32_t nwin = fk::rag_windows(G, cps_max);
+        if ((uint64_t)nwin * W < (uint64_t)G * cps_max) return fail + 2;
+        const uint32_t ntiles = (nblocks + G - 1) / G;
+        uint32_t nb = 0, nc = 0;   // the next (block, chunk) the walk must meet
+        auto skip_empty = [&] {
+            while (nb < nblocks && nc >= fk::rag_chunks(r.lens[nb], r.max_len)) ++nb, nc = 0;
+        };
+        std::vector<uint32_t> prefix(G + 1);
+        for (uint32_t wg = 0; wg < ntiles * nwin; ++wg) {
+            const fk::RagTile T = fk::rag_tile(wg, G, nwin, nblocks);
+            if (T.gt < 1 || T.gt > G || T.b0 + T.gt > nblocks || T.win >= nwin) return fail + 3;
+            prefix[0] = 0;
+            for (uint32_t g = 0; g < T.gt; ++g) prefix[g + 1] = prefix[g] + fk::rag_chunks(r.lens[T.b0 + g], r.max_len);
+            const uint32_t total = prefix[T.gt];
+            const fk::RagSpan sp = fk::rag_span(T.win, total);
+            if (sp.hi > total || sp.lo > sp.hi) return fail + 4;
+            if ((uint64_t)T.win * W >= total && sp.lo != sp.hi) return fail + 5;   // a window past the sum is empty
+            uint32_t rounds = 0;
+            for (uint32_t base = sp.lo; base < sp.hi; base += (uint32_t)fk::kThreads, ++rounds)
+                for (uint32_t lane = 0; lane < (uint32_t)fk::kThreads; ++lane) {
+                    const uint32_t t = base + lane;
+                    if (t >= sp.hi) continue;
+                    const uint32_t g = fk::rag_locate(prefix.data(), T.gt, t);
+                    if (g >= T.gt) return fail + 6;
+                    const uint32_t c = t - prefix[g];
+                    if (c >= fk::rag_chunks(r.lens[T.b0 + g], r.max_len)) return fail + 7;
+                    skip_empty();
+                    if (nb != T.b0 + g || nc != c) return fail + 8;   // in order: each pair once
+                    ++nc;
+                }
+            if (rounds > fk::kRagRounds) return fail + 9;
+        }
+        skip_empty();
+        if (nb != nblocks) return fail + 10;   // every pair met
+    }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the wide plan's coefficient
+// rows (fec_wide.hpp wide_logsum / wide_coef, the functions rs_plan_wide_kernel runs) equal the
+// rows of the inverse of the first-k-present submatrix of the systematic matrix, for 64 seeded
+// random recoverable masks per shape, plus all data lost where m >= k. 0 on success, else
+// 1000 * (shape index + 1) + mask index + 1.
+int fec__selftest_wide_plan(void) {
+    static const int shapes[][2] = {{32, 1}, {20, 13}, {33, 31}, {64, 16}, {128, 128}, {255, 1}, {1, 255}, {8, 4}};
+    uint8_t ex768[768];
+    for (uint32_t i = 0; i < 768; ++i) ex768[i] = fk::wide_exp768(i);
+    const uint8_t* lg = gf::kTables.log;
+    uint64_t seed = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const int k = sh[0], m = sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix(k, n);
+        if (M.empty()) return 1000 * si;
+        const int cases = 64 + (m >= k ? 1 : 0);
+        for (int ci = 0; ci < cases; ++ci) {
+            std::vector<uint8_t> pres((size_t)n, 1);
+            if (ci == 64) {
+                for (int i = 0; i < k; ++i) pres[i] = 0;
+            } else {
+                for (int lose = (int)(rnd() % (uint32_t)(m + 1)); lose > 0;) {
+                    const uint32_t i = rnd() % (uint32_t)n;
+                    if (pres[i]) {
+                        pres[i] = 0;
+                        --lose;
+                    }
+                }
+            }
+            std::vector<uint8_t> S, O;
+            for (int i = 0; i < n && (int)S.size() < k; ++i)
+                if (pres[i]) S.push_back((uint8_t)i);
+            for (int i = 0; i < k; ++i)
+                if (!pres[i]) O.push_back((uint8_t)i);
+            if (O.empty()) continue;
+            std::vector<uint8_t> sub((size_t)k * k);
+            for (int p = 0; p < k; ++p) memcpy(&sub[(size_t)p * k], &M[(size_t)S[p] * k], (size_t)k);
+            if (!rs::invert(k, sub.data())) return 1000 * si + ci + 1;
+            std::vector<uint32_t> D((size_t)k);
+            for (int p = 0; p < k; ++p) D[p] = fk::wide_logsum(lg, S.data(), (uint32_t)k, S[p], (uint32_t)p);
+            for (size_t r = 0; r < O.size(); ++r) {
+                const uint32_t N = fk::wide_logsum(lg, S.data(), (uint32_t)k, O[r], (uint32_t)k);
+                for (int p = 0; p < k; ++p)
+                    if (fk::wide_coef(ex768, lg, N, D[p], O[r], S[p]) != sub[(size_t)O[r] * k + p])
+                        return 1000 * si + ci + 1;
+            }
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -24,7 +24,7 @@ BIN = os.path.join(PKG, "_bin")
 SAN = os.path.join(PKG, "_san")
 INCLUDE = os.path.join(ROOT, "include")
 CLANG = "/opt/rocm/lib/llvm/bin/clang"
-HOST_SOURCES = ["fec_capi.cpp", "fec_scheme.cpp", "fec_batch.cpp", "fec_wire.cpp", "fec_go.cpp"]
+HOST_SOURCES = ["fec_capi.cpp", "fec_cores.cpp", "fec_host.cpp", "fec_selftest.cpp", "fec_scheme.cpp", "fec_batch.cpp", "fec_wire.cpp", "fec_go.cpp"]
 SAN_HOST = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
             "-Xarch_host", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
 SAN_C = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]

@@ -76,7 +76,7 @@ def test_lane_permtab_builder_matches_bytewise(fec):
 
 def test_copy_workers_cover_every_index_once(fec):
     # FEC_HOST's staging / scatter copies run through parallel_for on persistent copy workers
-    # (fec_capi.cpp CopyPool) or on threads made per call: every index exactly once, for sizes
+    # (fec_host.cpp CopyPool) or on threads made per call: every index exactly once, for sizes
     # around the part boundaries, 2..16 parts, four callers at once (no device needed; the
     # sanitized CPU run repeats it under ASan / UBSan)
     lib = ctypes.CDLL(fec._LIB_PATH)
@@ -85,7 +85,7 @@ def test_copy_workers_cover_every_index_once(fec):
 
 def test_store_policy_follows_region_hulls(fec):
     # sc1 stores only into a parity (or out) region apart from the shards read: the library's
-    # table of layouts (fec_capi.cpp fec__selftest_store_policy): split block-major and
+    # table of layouts (fec_selftest.cpp fec__selftest_store_policy): split block-major and
     # shard-major in one region apart, interleaved and row-alternating shard-major not, empty
     # batches nt, knob st_pol 2 sc1 always (no device needed: addresses are only compared)
     lib = ctypes.CDLL(fec._LIB_PATH)

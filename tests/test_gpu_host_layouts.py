@@ -16,7 +16,7 @@ bases interior pointers at addresses = 1, 2, 3 mod 4 across the cases) and "regi
 arena under hipHostRegister for the length of the case, FEC_HOST_PINNED, regions at odd offsets
 inside the registration).
 
-Routes. The pinned path picks its copies from the caller's strides (fec_capi.cpp): a chunk of nb
+Routes. The pinned path picks its copies from the caller's strides (fec_host.cpp): a chunk of nb
 blocks goes up as ONE linear copy of its span plus span_to_stage_kernel when
     4 * ((nb - 1) * dbs + (k - 1) * ss + L) <= 5 * nb * k * L        ("dense"),
 else as one 2D copy per data shard column; parity comes down as stage_to_packed_kernel plus ONE
@@ -560,3 +560,58 @@ def test_wide_host_call_writes_only_what_the_header_allows(codec, oracle, torch,
     def call(nb, data, dbs, parity, pbs, ss, masks, status, flag):
         return codec.rs_reconstruct_wide_raw(k, m, L, nb, data, dbs, parity, pbs, ss, masks, 2, status, flag)
     check_reconstruct(call, codec, fec, torch, kind, layout, k, m, L, WIDE_B, chunk, c, L + chunk + len(layout))
+
+
+_wide_fail_first = {}
+
+
+def wide_fail_first_case(oracle, fec, MUL):
+    """RS(31,2), 33 shards, so two mask words and the wide route; L = 17. Block 0 has k - 1 shards
+    present (a data shard and both parity shards lost) and fails; blocks 1 and 2 each lose one data
+    shard, block 2 parity 0 as well, so it reads the shard of the second mask word."""
+    if not _wide_fail_first:
+        k, m, L, nb = 31, 2, 17, 3
+        n = k + m
+        rng = np.random.default_rng(3102)
+        present = np.ones((nb, n), dtype=bool)
+        present[0, [3, k, k + 1]] = False
+        present[1, 30] = False
+        present[2, [0, k]] = False
+        assert present[0].sum() == k - 1 and list((~present[:, :k]).sum(axis=1)) == [1, 1, 1]
+        sh = np.zeros((nb, n, L), dtype=np.uint8)
+        sh[:, :k] = rng.integers(0, 256, (nb, k, L), dtype=np.uint8)
+        oracle.rs_encode(k, m, sh)
+        dmg = sh.copy()
+        dmg[~present] = ERASED
+        wide = np.zeros((nb, n, (L + 15) // 16 * 16), dtype=np.uint8)
+        wide[:, :, :L] = dmg
+        st_ref = ref_reconstruct(oracle, MUL, k, m, wide, present, L)
+        rec = np.ascontiguousarray(wide[:, :, :L])
+        assert list(st_ref) == [-4, 0, 0]
+        rebuilt = ~present[:, :k] & (st_ref == 0)[:, None]
+        assert rebuilt.sum() == 2 and np.array_equal(rec[:, :k][rebuilt], sh[:, :k][rebuilt])
+        untouched = np.ones((nb, n), dtype=bool)
+        untouched[:, :k] = ~rebuilt
+        assert np.array_equal(rec[untouched], dmg[untouched])
+        st_want = np.where(st_ref != 0, fec.FEC_ERR_TOO_FEW_SHARDS, 0).astype(np.int32)
+        masks = fec.wide_masks(present)
+        assert masks.shape == (nb, 2)
+        for a in (masks, dmg, rec, rebuilt, st_want):
+            a.setflags(write=False)
+        _wide_fail_first.update(masks=masks, dmg=dmg, rec=rec, rebuilt=rebuilt, st_want=st_want)
+    return _wide_fail_first
+
+
+@pytest.mark.parametrize("kind", ["pageable", "pinned"])
+def test_wide_host_failing_block_before_clean_chunks(codec, oracle, torch, fec, MUL, kind):
+    """Chunks of one block: the failing block is the first chunk, and two chunks that rebuild follow
+    it. check_reconstruct runs the call with block_status given and with NULL: both return
+    FEC_ERR_TOO_FEW_SHARDS, the statuses are [-4, 0, 0], the arena equals the model, fec_sync is
+    FEC_OK."""
+    k, m, L = 31, 2, 17
+    c = wide_fail_first_case(oracle, fec, MUL)
+    assert list(c["st_want"]) == [fec.FEC_ERR_TOO_FEW_SHARDS, 0, 0]
+
+    def call(nb, data, dbs, parity, pbs, ss, masks, status, flag):
+        return codec.rs_reconstruct_wide_raw(k, m, L, nb, data, dbs, parity, pbs, ss, masks, 2, status, flag)
+    check_reconstruct(call, codec, fec, torch, kind, "slack_split", k, m, L, 3, 1, c, 1)

@@ -194,7 +194,7 @@ def test_verify_block_spanning_workgroups(codec, torch, fec, k, m):
 
 
 def test_verify_batch_cut_into_two_launches(codec, torch, fec):
-    """The smallest batch the encode's launch limit (fec_capi.cpp kMaxItems chunks per launch) cuts in
+    """The smallest batch the encode's launch limit (fec_ctx.hpp kMaxItems chunks per launch) cuts in
     two: 2^31 / 4375 + 1 blocks of 70 000-byte shards, the last block alone in the second launch.
     Verify only reads its shards, so the blocks may overlap: RS(1,2) with both block strides 16 makes
     block b the window [16 b, 16 b + 70 000) of one data and one parity stream of 7.9 MB, and the
@@ -202,7 +202,7 @@ def test_verify_batch_cut_into_two_launches(codec, torch, fec):
     to blocks t - 4374 .. t: a flip in the first chunk makes block 0 bad alone, in the last chunk the
     last block alone, and in chunk t = the second launch's first block, 4375 blocks across the cut,
     which the count must add up over both launches."""
-    src = open(os.path.join(ROOT, "0xfec_amd", "csrc", "fec_capi.cpp")).read()
+    src = open(os.path.join(ROOT, "0xfec_amd", "csrc", "fec_ctx.hpp")).read()
     lim = re.search(r"kMaxItems\s*=\s*uint64_t\(1\)\s*<<\s*(\d+)\s*;", src)
     assert lim, "the encode's launch limit"
     max_items = 1 << int(lim.group(1))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Chunk size and parity-plane policy of the host-resident pipeline (fec_capi.cpp HostPipe),
+"""Chunk size and parity-plane policy of the host-resident pipeline (fec_ctx.hpp HostPipe, fec_host.cpp),
 measured with bench.py's own host_resident() step (RS(8,12) encode + single-erasure reconstruct,
 packed pinned and pageable host buffers).
 

@@ -1,5 +1,5 @@
 // pcie_duplex_probe.hip — what the host link of one MI355X can move, per direction and at once.
-// Decides the shape of the host-resident pipeline (fec_capi.cpp, FEC_HOST / FEC_HOST_PINNED):
+// Decides the shape of the host-resident pipeline (fec_host.cpp, FEC_HOST / FEC_HOST_PINNED):
 // whether an H2D stream and a D2H stream overlap (full duplex), whether two H2D streams beat one,
 // and whether kernels reading / writing pinned host memory directly ("zero-copy") can stand in
 // for either DMA direction while the other runs.
