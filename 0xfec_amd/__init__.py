@@ -51,6 +51,8 @@ FEC_HOST = 1
 FEC_HOST_PINNED = 2
 FEC_MAX_DECODE_SHARDS = 32
 FEC_MAX_WIDE_SHARDS = 256
+FEC_LOCATE_CLEAN = -1
+FEC_LOCATE_UNKNOWN = -2
 
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -82,6 +84,7 @@ lib.fec_rs_reconstruct_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz,
 lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _i, _vp,
                                             _i]
 lib.fec_rs_verify_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
+lib.fec_rs_locate_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i]
 lib.fec_rs_reconstruct_some_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
 lib.fec_rs_update_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
 lib.fec_rs_encode_idx_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
@@ -477,6 +480,29 @@ class Codec:
 
     def rs_verify_split(self, k, m, data, parity, status, count=None, shard_len=None):
         return self._verify(k, m, _Layout(k, m, data, parity, _SOME), status, count, shard_len)
+
+    # ---- locate (FEC_DEVICE only; device tensors): bad_shard is an int32 device tensor [B] that
+    # receives FEC_LOCATE_CLEAN, the corrupt shard's index, or FEC_LOCATE_UNKNOWN per block;
+    # present_out an optional 4-byte integer device tensor [B, W], FEC_MASK_WORDS(k + m) <= W <= 8, that
+    # receives the present masks which heal the located blocks (W = 1: rs_reconstruct_some's masks);
+    # counts an optional 4-byte integer device tensor of two elements (located, unknown).
+    def rs_locate_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, bad_shard, present_out=None,
+                      mask_words=None, counts=None, flags=FEC_DEVICE):
+        return lib.fec_rs_locate_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, bad_shard,
+                                       present_out, (k + m + 31) // 32 if mask_words is None else mask_words, counts,
+                                       flags)
+
+    def _locate(self, k, m, lay, bad_shard, present_out, counts, shard_len):
+        pa, W = (None, None) if present_out is None else self._col_masks(present_out, lay.B)
+        ca = None if counts is None else self._words_addr(counts, 2, "counts")
+        return _check(self.rs_locate_raw(k, m, *lay.args(shard_len), self._words_addr(bad_shard, lay.B, "bad_shard"),
+                                         pa, W, ca), "fec_rs_locate_batch")
+
+    def rs_locate(self, k, m, shards, bad_shard, present_out=None, counts=None, shard_len=None):
+        return self._locate(k, m, _Layout(k, m, shards, None, _SOME), bad_shard, present_out, counts, shard_len)
+
+    def rs_locate_split(self, k, m, data, parity, bad_shard, present_out=None, counts=None, shard_len=None):
+        return self._locate(k, m, _Layout(k, m, data, parity, _SOME), bad_shard, present_out, counts, shard_len)
 
     def _reconstruct_some(self, k, m, lay, masks, want, status, shard_len):
         wa = None if want is None else self._words_addr(want, lay.B, "want")

@@ -7,11 +7,13 @@
 // without a HIP device every compute entry point fails with FEC_ERR_NO_DEVICE / FEC_ERR_HIP.
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <functional>
 
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
+#include "fec_locate.hpp"
 #include "gf256.h"
 #include "rs_matrix.hpp"
 
@@ -117,6 +119,27 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 }
             HIP_TRY(hipMalloc(&c.d_single, st.size() * 4));
             HIP_TRY(hipMemcpy(c.d_single, st.data(), st.size() * 4, hipMemcpyHostToDevice));
+        }
+        {   // the locate call's ratio -> column table and the field's inverses (fec_locate.hpp)
+            uint8_t lt[fk::kLocateTabBytes];
+            if (!fk::locate_table(lt, c.matrix.data() + (size_t)k * k, (uint32_t)k, (uint32_t)m))
+                return FEC_ERR_INVALID_ARG;
+            HIP_TRY(hipMalloc(&c.d_loctab, sizeof(lt)));
+            HIP_TRY(hipMemcpy(c.d_loctab, lt, sizeof(lt), hipMemcpyHostToDevice));
+        }
+        if (fk::locate_needs_carry_tabs((uint32_t)k, (uint32_t)m)) {
+            // locate's later passes, each row 0's tables followed by its own rows' (fec_locate.hpp)
+            const size_t row = (size_t)k * 8, slab = fk::kLocateRows * row;
+            const uint32_t later = fk::locate_passes((uint32_t)m) - 1;
+            std::vector<uint32_t> carry(later * slab, 0);
+            for (uint32_t p = 0; p < later; ++p) {
+                const int r0 = 1 + (fk::kLocateRows - 1) * (int)(p + 1);
+                const int rows = std::min(fk::kLocateRows - 1, m - r0);
+                memcpy(&carry[p * slab], tabs.data(), row * 4);
+                memcpy(&carry[p * slab + row], &tabs[r0 * row], rows * row * 4);
+            }
+            HIP_TRY(hipMalloc(&c.d_loc_carry, carry.size() * 4));
+            HIP_TRY(hipMemcpy(c.d_loc_carry, carry.data(), carry.size() * 4, hipMemcpyHostToDevice));
         }
         const std::vector<uint8_t> leaves = dyadic_leaves(c.matrix, k, m);
         if (!leaves.empty() && leaves.size() <= (size_t)m * k) {   // staged like m x k tables
@@ -275,6 +298,8 @@ void fec_ctx_destroy(fec_ctx* ctx) {
         if (kv.second.d_single) (void)hipFree(kv.second.d_single);
         if (kv.second.d_single_coef) (void)hipFree(kv.second.d_single_coef);
         if (kv.second.d_dall) (void)hipFree(kv.second.d_dall);
+        if (kv.second.d_loctab) (void)hipFree(kv.second.d_loctab);
+        if (kv.second.d_loc_carry) (void)hipFree(kv.second.d_loc_carry);
     }
     if (ctx->own) (void)hipStreamSynchronize(ctx->own);
     if (ctx->stream && ctx->stream != ctx->own) (void)hipStreamSynchronize(ctx->stream);
@@ -596,6 +621,26 @@ int fec_rs_reconstruct_some_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
     return rs_reconstruct_some_device(ctx, k, m, shard_len, nblocks, data, data_block_stride,
                                       const_cast<uint8_t*>(par), parity_block_stride, shard_stride, present_mask,
                                       want_mask, block_status, ctx->d_err);
+}
+
+// ---------------------------------------------------------------- locate
+// mask_words is checked whether or not present_out is given.
+int fec_rs_locate_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
+                        size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                        size_t shard_stride, int32_t* bad_shard, uint32_t* present_out, size_t mask_words,
+                        uint32_t* counts, int flags) {
+    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &parity, parity_block_stride,
+           shard_stride};
+    c.null_arg = !bad_shard;
+    c.wide = true, c.mask_words = mask_words;
+    c.words[0] = {present_out, bad_shard};
+    c.words[1] = {counts, nullptr};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_locate_device(ctx, code, shard_len, nblocks,
+                            {data, data_block_stride, parity, parity_block_stride, shard_stride, bad_shard,
+                             present_out, mask_words, counts});
 }
 
 // ---------------------------------------------------------------- update, encode-idx

@@ -5,6 +5,7 @@
 
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
+#include "fec_locate.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
 #include "fec_update.hpp"
@@ -340,6 +341,69 @@ int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks,
     });
 }
 
+// Locate (fec_locate.hip; LocateCall, fec_ctx.hpp, holds a call's regions and outputs). pass(args)
+// for every kernel launch of a call and fin(args) once per slice after its passes, until one fails:
+// verify's cut under kMaxItems items; each pass takes parity row 0 and up to 15 rows from
+// r0 = 1, 16, 31, ... (a code of one parity row: row 0 alone; of none: no pass). No device work
+// (fec__selftest_locate_slices calls it without one).
+template <class P, class F>
+static int locate_launches(const Code* code, size_t len, size_t nblocks, const LocateCall& c, P pass, F fin) {
+    const uint32_t cps = chunks_of(len);
+    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+        for (int r0 = 1; code->m > 0 && (r0 == 1 || r0 < code->m); r0 += fk::kLocateRows - 1) {
+            fk::LocateArgs a{};
+            a.in = c.data + b0 * c.dbs;
+            a.par = c.parity + b0 * c.pbs;
+            a.in_bs = c.dbs;
+            a.par_bs = c.pbs;
+            a.ss = c.ss;
+            a.k = (uint32_t)code->k;
+            a.m = (uint32_t)code->m;
+            a.r0 = (uint32_t)r0;
+            a.rows = 1u + (uint32_t)std::min(fk::kLocateRows - 1, code->m - r0);
+            a.len = (uint32_t)len;
+            a.cps = cps;
+            a.total = (uint32_t)(nb * cps);
+            a.div_cps = fk::make_fastdiv(cps);
+            if (r0 > 1 && code->d_loc_carry) {   // the pass's slab: row 0's tables, then its rows'
+                a.tabs0 = code->d_loc_carry + (size_t)(r0 / (fk::kLocateRows - 1) - 1) * fk::kLocateRows * code->k * 8;
+                a.tabs = a.tabs0 + (size_t)code->k * 8;
+            } else {
+                a.tabs0 = code->d_tabs;
+                a.tabs = code->d_tabs + (size_t)r0 * code->k * 8;
+            }
+            a.loctab = code->d_loctab;
+            a.verdict = c.verdict + b0;
+            const int rc = pass(a);
+            if (rc) return rc;
+        }
+        fk::LocateFinArgs f{};
+        f.verdict = c.verdict + b0;
+        f.present = c.present ? c.present + b0 * c.mask_words : nullptr;
+        f.counts = c.counts;
+        f.nblocks = (uint32_t)nb;
+        f.n = (uint32_t)(code->k + code->m);
+        f.mask_words = (uint32_t)c.mask_words;
+        return fin(f);
+    });
+}
+
+// Verdicts pre-set to clean and the counts to 0 on the stream, as verify presets its statuses.
+int rs_locate_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateCall& c) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c.verdict, fk::kLocateClean, nblocks, ctx->stream));
+    if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 2 * sizeof(uint32_t), ctx->stream));
+    return locate_launches(
+        code, len, nblocks, c,
+        [&](const fk::LocateArgs& a) -> int {
+            HIP_TRY(fk::launch_rs_locate(a, flat_grid(a.total), ctx->stream));
+            return FEC_OK;
+        },
+        [&](const fk::LocateFinArgs& f) -> int {
+            HIP_TRY(fk::launch_rs_locate_finalize(f, ctx->stream));
+            return FEC_OK;
+        });
+}
+
 // Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
 // the wide tile, storing into both regions.
 int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
@@ -532,6 +596,114 @@ int fec__selftest_update_slices(void) {
     fill_update_launch(a, &code, 16, per, 1, L, e);
     code.d_tabs = nullptr;
     if (a.old != nullptr || (uintptr_t)a.in != in0 + per * in_bs) return 3;
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the launches of a locate call
+// that the launch limit cuts, for m = 2, 16, 17, 31, 32, 40 (and 1 and 0: one pass of row 0 alone,
+// and none). k = 5, 70 000-byte shards, one block more than kMaxItems / 4375: two slices (490 853
+// blocks, then one), each its passes and then its finalize. Pass p takes row 0 and the rows from
+// r0 = 1 + 15 p: min(15, m - r0) of them. Every launch's data and parity bases, rows, tables, item
+// count and verdict pointer, and every finalize's verdict, mask and count pointers, are compared
+// with values worked out here from the call's strides. 0 on success, else
+// 1000 * (index of m + 1) + 10 * (launch index + 1) + the failing field.
+int fec__selftest_locate_slices(void) {
+    const int k = 5;
+    const size_t L = 70000, cps = 4375, per = 490853, B = per + 1, W = 3;
+    if (per != (size_t)(kMaxItems / cps)) return 1;
+    const size_t ss = 70016, dbs = k * ss + 48;
+    const uintptr_t in0 = uintptr_t(1) << 40, par0 = uintptr_t(3) << 40, mask0 = uintptr_t(4) << 40,
+                    tab0 = uintptr_t(5) << 40, ver0 = uintptr_t(6) << 40, cnt0 = uintptr_t(7) << 40,
+                    loc0 = uintptr_t(8) << 40;
+    static const int ms[] = {2, 16, 17, 31, 32, 40, 1, 0};
+    static const int want_passes[] = {1, 1, 2, 2, 3, 3, 1, 0};
+    int mi = 0;
+    for (int m : ms) {
+        const int base = 1000 * ++mi;
+        const size_t pbs = (size_t)m * ss + 32;
+        Code code;
+        code.k = k;
+        code.m = m;
+        code.d_tabs = (uint32_t*)tab0;
+        code.d_loctab = (uint8_t*)loc0;
+        const LocateCall c{(const uint8_t*)in0, dbs, (const uint8_t*)par0, pbs, ss, (int32_t*)ver0,
+                           (uint32_t*)mask0, W, (uint32_t*)cnt0};
+        std::vector<fk::LocateArgs> got;
+        std::vector<fk::LocateFinArgs> fins;
+        std::vector<size_t> fin_after;   // launches emitted before each finalize
+        const int rc = locate_launches(
+            &code, L, B, c,
+            [&](const fk::LocateArgs& a) -> int {
+                got.push_back(a);
+                return FEC_OK;
+            },
+            [&](const fk::LocateFinArgs& f) -> int {
+                fins.push_back(f);
+                fin_after.push_back(got.size());
+                return FEC_OK;
+            });
+        code.d_tabs = nullptr;
+        code.d_loctab = nullptr;
+        const size_t np = (size_t)want_passes[mi - 1];
+        if (rc != FEC_OK || got.size() != 2 * np || fins.size() != 2) return base + 2;
+        for (size_t i = 0; i < got.size(); ++i) {
+            const fk::LocateArgs& a = got[i];
+            const int fail = base + 10 * ((int)i + 1);
+            const size_t b0 = (i / np) * per, nb = i / np ? 1 : per, r0 = 1 + 15 * (i % np);
+            const size_t rows = 1 + std::min<size_t>(15, (size_t)m - r0);   // row 0 among them
+            if ((uintptr_t)a.in != in0 + b0 * dbs || a.in_bs != dbs || a.ss != ss) return fail + 1;
+            if ((uintptr_t)a.par != par0 + b0 * pbs || a.par_bs != pbs) return fail + 2;
+            if (a.r0 != r0 || a.rows != rows || a.k != (uint32_t)k || a.m != (uint32_t)m) return fail + 4;
+            if (a.total != nb * cps || a.cps != cps || a.len != L || a.div_cps.d != cps) return fail + 5;
+            if ((uintptr_t)a.tabs0 != tab0 || (uintptr_t)a.tabs != tab0 + r0 * k * 8 * 4) return fail + 6;
+            if ((uintptr_t)a.loctab != loc0) return fail + 7;
+            if ((uintptr_t)a.verdict != ver0 + b0 * 4) return fail + 8;
+        }
+        for (size_t s = 0; s < 2; ++s) {
+            const fk::LocateFinArgs& f = fins[s];
+            const int fail = base + 500 + 10 * (int)s;
+            const size_t b0 = s * per, nb = s ? 1 : per;
+            if (fin_after[s] != (s + 1) * np) return fail + 1;   // after its slice's passes, before the next's
+            if ((uintptr_t)f.verdict != ver0 + b0 * 4 || f.nblocks != nb) return fail + 2;
+            if ((uintptr_t)f.present != mask0 + b0 * W * 4 || f.mask_words != W) return fail + 3;
+            if ((uintptr_t)f.counts != cnt0 || f.n != (uint32_t)(k + m)) return fail + 4;
+        }
+    }
+    // no masks asked for: none in any finalize
+    Code code;
+    code.k = k;
+    code.m = 2;
+    code.d_tabs = (uint32_t*)tab0;
+    const LocateCall c{(const uint8_t*)in0, dbs, (const uint8_t*)par0, 2 * ss, ss, (int32_t*)ver0, nullptr, W, nullptr};
+    int bad = 0;
+    (void)locate_launches(
+        &code, L, B, c, [&](const fk::LocateArgs&) -> int { return FEC_OK; },
+        [&](const fk::LocateFinArgs& f) -> int {
+            if (f.present || f.counts) ++bad;
+            return FEC_OK;
+        });
+    if (bad) return 3;
+    // a code with a table for its later passes (k > 128, m > 16): pass 0 reads the code's table, pass p
+    // slab p - 1 of 16 * k PermTabs, row 0's first
+    const uintptr_t car0 = uintptr_t(9) << 40;
+    code.k = 130;
+    code.m = 40;
+    code.d_tabs = (uint32_t*)tab0;
+    code.d_loc_carry = (uint32_t*)car0;
+    std::vector<fk::LocateArgs> got;
+    (void)locate_launches(
+        &code, 16, 1, c,
+        [&](const fk::LocateArgs& a) -> int {
+            got.push_back(a);
+            return FEC_OK;
+        },
+        [&](const fk::LocateFinArgs&) -> int { return FEC_OK; });
+    code.d_tabs = code.d_loc_carry = nullptr;
+    if (got.size() != 3 || (uintptr_t)got[0].tabs0 != tab0 || (uintptr_t)got[0].tabs != tab0 + 130 * 8 * 4) return 4;
+    for (size_t p = 1; p < 3; ++p)
+        if ((uintptr_t)got[p].tabs0 != car0 + (p - 1) * 16 * 130 * 8 * 4 ||
+            (uintptr_t)got[p].tabs != (uintptr_t)got[p].tabs0 + 130 * 8 * 4)
+            return 5;
     return 0;
 }
 

@@ -24,6 +24,8 @@ struct Code {
     uint32_t* d_single_coef = nullptr;   // their coefficient bytes, (k*m) rows of ceil(k/4) dwords
     std::vector<uint32_t> single_coef;   // host copy
     uint8_t* d_dall = nullptr;     // n bytes: sum_{t != s} log(s ^ t) mod 255 (sorted plans)
+    uint8_t* d_loctab = nullptr;   // m > 0: the locate call's table (fec_locate.hpp locate_table)
+    uint32_t* d_loc_carry = nullptr;   // k > 128, m > 16: PermTabs of locate's later passes, a slab per pass
 };
 
 // Bytes of staged shards per FEC_HOST chunk (x2 buffers, in and out).
@@ -153,6 +155,18 @@ struct UpdateCall {
     size_t mask_words;
 };
 int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const UpdateCall& u);
+// Locate (fec_locate.hip): the regions and outputs of one call (present and counts may be null).
+struct LocateCall {
+    const uint8_t* data;
+    size_t dbs;
+    const uint8_t* parity;
+    size_t pbs, ss;
+    int32_t* verdict;
+    uint32_t* present;
+    size_t mask_words;
+    uint32_t* counts;
+};
+int rs_locate_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateCall& c);
 int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
                                uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, const uint32_t* want,
                                int32_t* status, int* err);

@@ -9,6 +9,7 @@
 
 #include "../../include/fec_hip.h"
 #include "fec_kernels.hpp"
+#include "fec_locate.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
 #include "fec_wide.hpp"
@@ -178,6 +179,143 @@ int fec__selftest_some_plan(void) {
             if (fk::some_plan_record(rec2.data(), lay, few, few, k, n, ex768, lg) != 0 || rec2[lay.nout_off]) return fail;
         }
     }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the locate call's arithmetic
+// (fec_locate.hpp: locate_table, locate_chunk, locate_merge, the functions rs_locate_kernel runs)
+// against the brute-force definition, on syndromes. Per code: the table names column j at
+// M[k+1][j] / M[k][j] and nothing else, and holds the field's inverses. Then seeded blocks of three
+// 16-byte chunks in twelve corruption patterns (none; one data shard: one byte, bytes in several
+// chunks, every byte; parity row 0, any parity row, the last one; two data shards in one chunk, in
+// two chunks; a data and a parity shard in two chunks; for m > 16 a data shard whose rows 16 .. carry
+// another error of the same column; t >= 2 random shards): the chunks are classified pass by pass
+// (row 0 and 15 rows from r0 = 1, 16, ...) and merged into one word, in ascending and in descending
+// chunk order, and the word must be what the definition gives: clean if every syndrome is zero, else
+// (m >= 2) the one shard s for which some replacement of s alone explains every syndrome (a parity
+// row that is the only nonzero one; a column j with S_i = M[k+i][j] * S_0 / M[k][j] in every row and
+// byte), else unknown. 0 on success, else 1000 * (code index + 1) + case index + 1.
+int fec__selftest_locate(void) {
+    static const int shapes[][2] = {{1, 2}, {2, 2}, {8, 4}, {20, 10}, {3, 20}, {2, 33}, {254, 2}, {31, 1}};
+    constexpr int R = fk::kLocateRows;
+    constexpr uint32_t C = 3, W = 16 * C;   // chunks and bytes per shard
+    uint64_t seed = 0xA0761D6478BD642Full;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    auto nzbyte = [&rnd]() -> uint8_t { return (uint8_t)(1 + rnd() % 255); };
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1];
+        const std::vector<uint8_t> M = rs::build_matrix((int)k, (int)(k + m));
+        if (M.empty()) return 1000 * si;
+        const uint8_t* P = M.data() + (size_t)k * k;   // parity rows
+        uint8_t tab[fk::kLocateTabBytes];
+        if (!fk::locate_table(tab, P, k, m)) return 1000 * si;
+        for (uint32_t a = 1; a < 256; ++a)
+            if (gf::mul((uint8_t)a, tab[256 + a]) != 1) return 1000 * si;
+        if (tab[256] != 0) return 1000 * si;
+        uint32_t named = 0;
+        for (uint32_t r = 0; r < 256; ++r) named += tab[r] != 0xFF;
+        if (named != (m >= 2 ? k : 0)) return 1000 * si;
+        for (uint32_t j = 0; m >= 2 && j < k; ++j)
+            if (tab[gf::mul(P[k + j], gf::inv(P[j]))] != j) return 1000 * si;
+        std::vector<gf::PermTab> T((size_t)m * k);
+        for (size_t i = 0; i < T.size(); ++i) T[i] = gf::make_permtab(P[i]);
+
+        for (int ci = 0; ci < 12 * 8; ++ci) {
+            const int fail = 1000 * si + ci + 1;
+            std::vector<uint8_t> S((size_t)m * W, 0);
+            auto data_err = [&](uint32_t j, uint32_t x, uint8_t e, uint32_t row_lo = 0) {
+                for (uint32_t r = row_lo; r < m; ++r) S[r * W + x] ^= gf::mul(P[r * k + j], e);
+            };
+            auto par_err = [&](uint32_t i, uint32_t x, uint8_t e) { S[i * W + x] ^= e; };
+            const uint32_t j1 = rnd() % k, j2 = k > 1 ? (j1 + 1 + rnd() % (k - 1)) % k : j1;
+            const uint32_t x1 = rnd() % 16, x2 = 16 + rnd() % 16, x3 = 32 + rnd() % 16;
+            switch (ci % 12) {
+                case 0: break;
+                case 1: data_err(j1, x2, (uint8_t)(1u << (rnd() % 8))); break;
+                case 2: data_err(j1, x1, nzbyte()), data_err(j1, x2, nzbyte()), data_err(j1, x3, nzbyte()); break;
+                case 3:
+                    for (uint32_t x = 0; x < W; ++x) data_err(j1, x, nzbyte());
+                    break;
+                case 4: par_err(0, x1, nzbyte()), par_err(0, x3, nzbyte()); break;
+                case 5: par_err(rnd() % m, x2, nzbyte()); break;
+                case 6: par_err(m - 1, x1, nzbyte()), par_err(m - 1, x2, nzbyte()); break;
+                case 7:   // (k = 1: a data and a parity shard)
+                    data_err(j1, x1, nzbyte());
+                    if (k > 1) data_err(j2, (x1 + 1) % 16, nzbyte());
+                    else par_err(rnd() % m, (x1 + 1) % 16, nzbyte());
+                    break;
+                case 8:
+                    data_err(j1, x1, nzbyte());
+                    if (k > 1) data_err(j2, x3, nzbyte());
+                    else par_err(rnd() % m, x3, nzbyte());
+                    break;
+                case 9: data_err(j1, x1, nzbyte()), par_err(rnd() % m, x2, nzbyte()); break;
+                case 10: {   // every pass agrees on the column, the passes disagree on the error
+                    const uint8_t e = nzbyte();
+                    data_err(j1, x2, e);
+                    if (m > 16) data_err(j1, x2, nzbyte(), 16);   // rows 16 ..: e ^ another byte
+                    break;
+                }
+                default:
+                    for (uint32_t t = 2 + rnd() % (m + 1); t > 0; --t) {
+                        const uint32_t s = rnd() % (k + m);
+                        if (s < k) data_err(s, rnd() % W, nzbyte());
+                        else par_err(s - k, rnd() % W, nzbyte());
+                    }
+            }
+            // the definition
+            int32_t want = fk::kLocateClean;
+            if (std::any_of(S.begin(), S.end(), [](uint8_t v) { return v != 0; })) {
+                int found = 0;
+                want = fk::kLocateUnknown;
+                for (uint32_t i = 0; m >= 2 && i < m; ++i) {
+                    bool ok = true;
+                    for (uint32_t r = 0; r < m; ++r)
+                        for (uint32_t x = 0; x < W; ++x) ok = ok && (r == i || S[r * W + x] == 0);
+                    if (ok) want = (int32_t)(k + i), ++found;
+                }
+                for (uint32_t j = 0; m >= 2 && j < k; ++j) {
+                    bool ok = true;
+                    for (uint32_t x = 0; x < W; ++x) {
+                        const uint8_t e = gf::mul(gf::inv(P[j]), S[x]);
+                        for (uint32_t r = 0; r < m; ++r) ok = ok && S[r * W + x] == gf::mul(P[r * k + j], e);
+                    }
+                    if (ok) want = (int32_t)j, ++found;
+                }
+                if (found > 1) return fail;   // (distance m + 1 >= 3 rules it out)
+            }
+            for (int order = 0; order < 2; ++order) {
+                int32_t word = fk::kLocateClean;
+                for (uint32_t r0 = 1; m > 0 && (r0 == 1 || r0 < m); r0 += R - 1) {
+                    const uint32_t rows = 1 + std::min<uint32_t>(R - 1, m - r0);
+                    std::vector<gf::PermTab> Tp(T.begin(), T.begin() + k);   // row 0's tables, then the pass's
+                    Tp.insert(Tp.end(), T.begin() + (size_t)r0 * k, T.begin() + (size_t)(r0 + rows - 1) * k);
+                    for (uint32_t cc = 0; cc < C; ++cc) {
+                        const uint32_t c = order ? C - 1 - cc : cc;
+                        uint32_t acc[R][4] = {};
+                        for (uint32_t i = 0; i < rows; ++i)
+                            memcpy(acc[i], &S[fk::locate_row(i, r0) * W + 16 * c], 16);
+                        const int32_t p = fk::locate_chunk<R>(acc, rows, r0, k, m, Tp.data(), tab, word);
+                        word = fk::locate_merge(word, p);
+                    }
+                }
+                if (word != want) return fail;
+            }
+        }
+    }
+    // the merge rule, every pair
+    const int32_t CL = fk::kLocateClean, UN = fk::kLocateUnknown;
+    if (fk::locate_merge(CL, CL) != CL || fk::locate_merge(CL, 7) != 7 || fk::locate_merge(CL, UN) != UN) return 1;
+    if (fk::locate_merge(7, CL) != 7 || fk::locate_merge(7, 7) != 7 || fk::locate_merge(7, 8) != UN) return 2;
+    if (fk::locate_merge(7, UN) != UN || fk::locate_merge(UN, CL) != UN || fk::locate_merge(UN, 7) != UN) return 3;
+    if (fk::locate_merge(UN, UN) != UN || fk::locate_merge(0, 255) != UN || fk::locate_merge(0, 0) != 0) return 4;
     return 0;
 }
 

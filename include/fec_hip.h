@@ -25,6 +25,9 @@
  *                               (2 + biggestSourceSymbolLenSoFar, reed_solomon.go:47,80)
  *   fec_rs_verify_batch         Encoder.Verify(shards), batched: one verdict per block (klauspost's
  *                               interface; the reference does not call it)
+ *   fec_rs_locate_batch         no counterpart: which shard of a block that fails Verify is the corrupt
+ *                               one (klauspost's advice is to leave out each shard in turn, reconstruct
+ *                               and verify again), and the present mask that heals the block
  *   fec_rs_reconstruct_some_batch
  *                               Encoder.Reconstruct (want_mask NULL) and Encoder.ReconstructSome, in
  *                               place: missing parity shards are rebuilt too (klauspost's interface;
@@ -287,6 +290,53 @@ int fec_rs_verify_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
                         const uint8_t *parity, size_t parity_block_stride,
                         size_t shard_stride, int32_t *block_status,
                         uint32_t *mismatch_count, int flags);
+
+/* Locate the corrupt shard of a block that fails verify. All k + m shards of a block are given (no
+ * erasures); only bytes [0, shard_len) of each slot count. A block is consistent if its parity equals
+ * what fec_rs_encode_batch would write from its data. bad_shard[b] receives
+ *   FEC_LOCATE_CLEAN    the block is consistent
+ *   s in [0, k + m)     the block is not consistent, m >= 2, and replacing the contents of shard s
+ *                       alone (data for s < k, parity s - k otherwise) can make it consistent; at most
+ *                       one such s exists, because the code has distance m + 1 >= 3
+ *   FEC_LOCATE_UNKNOWN  the block is not consistent and no single shard explains it; with m == 1
+ *                       every inconsistent block (one parity row cannot tell the shards apart)
+ * With m == 0 every block is clean. One corrupt shard, any bytes of it, is always located when
+ * m >= 2; t corrupt shards with 2 <= t < m always give FEC_LOCATE_UNKNOWN; with t >= m a wrong shard
+ * can be named, as by any decoder past its distance.
+ *
+ * Outputs, all device memory, 4-byte aligned (else FEC_ERR_ALIGNMENT); the call sets every word of
+ * each, the caller need not clear them:
+ *   bad_shard    (required) nblocks verdicts
+ *   present_out  (optional) nblocks x mask_words words in the wide calls' bit order: bits [0, k + m)
+ *                set, except bit s of a located block; bits at and above k + m zero. With k + m <= 32
+ *                and mask_words == 1 it is the present_mask with which fec_rs_reconstruct_some_batch
+ *                rebuilds exactly the located shard, data or parity; for wider codes that of
+ *                fec_rs_reconstruct_wide_batch (a located parity shard is then re-encoded).
+ *                FEC_MASK_WORDS(k + m) <= mask_words <= 8, else FEC_ERR_INVALID_ARG, whether or not
+ *                present_out is given
+ *   counts       (optional) two uint32: when the call's work completes on the stream, [0] holds the
+ *                located blocks and [1] the unknown ones
+ * Nothing else is written; data and parity are only read, and bytes at and past shard_len of a slot
+ * never influence a verdict. A corrupt block is a result, not an error: the sticky word is untouched
+ * and fec_sync() returns FEC_OK.
+ *
+ * Every code the encode takes: k >= 1, m >= 0, k + m <= 256. FEC_DEVICE only: any other `flags` value
+ * returns FEC_ERR_INVALID_ARG. Layout and alignment rules are the uniform calls'; the host-side
+ * checks run in their order: shard counts, k + m > 256, flags, shard_len (0: FEC_ERR_SHARD_NO_DATA,
+ * above 2^30: FEC_ERR_INVALID_ARG), mask_words, the ctx, nblocks == 0 (FEC_OK, nothing touched), null
+ * pointers (bad_shard, data, and parity when m > 0), the layouts, the word alignment.
+ *
+ * Cost. A clean batch is read once per pass and no atomic is issued, as by fec_rs_verify_batch; a
+ * pass takes parity row 0 and 15 further rows (verify: 16 rows), so codes of m > 16 read row 0 again
+ * in each pass and some of them (m = 32, 47, 48, ...) take one pass more than verify. */
+#define FEC_LOCATE_CLEAN (-1)
+#define FEC_LOCATE_UNKNOWN (-2)
+int fec_rs_locate_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                        const uint8_t *data, size_t data_block_stride,
+                        const uint8_t *parity, size_t parity_block_stride,
+                        size_t shard_stride, int32_t *bad_shard,
+                        uint32_t *present_out, size_t mask_words,
+                        uint32_t *counts, int flags);
 
 /* RS Reconstruct / ReconstructSome, in place: as fec_rs_reconstruct_batch (k + m <=
  * FEC_MAX_DECODE_SHARDS, one uint32 present mask per block), but missing PARITY shards are rebuilt
