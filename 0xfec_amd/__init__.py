@@ -53,6 +53,7 @@ FEC_MAX_DECODE_SHARDS = 32
 FEC_MAX_WIDE_SHARDS = 256
 FEC_LOCATE_CLEAN = -1
 FEC_LOCATE_UNKNOWN = -2
+FEC_LOCATE_MAX_BAD = 8
 
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -85,6 +86,7 @@ lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp
                                             _i]
 lib.fec_rs_verify_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_locate_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i]
+lib.fec_rs_locate_multi_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i, _vp, _vp, _sz, _vp, _i]
 lib.fec_rs_reconstruct_some_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
 lib.fec_rs_update_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
 lib.fec_rs_encode_idx_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
@@ -503,6 +505,33 @@ class Codec:
 
     def rs_locate_split(self, k, m, data, parity, bad_shard, present_out=None, counts=None, shard_len=None):
         return self._locate(k, m, _Layout(k, m, data, parity, _SOME), bad_shard, present_out, counts, shard_len)
+
+    # ---- locate-multi (FEC_DEVICE only; device tensors; m <= 16): up to min(max_bad, m // 2) corrupt
+    # shards per block. bad_count is an int32 device tensor [B] that receives 0, the number of corrupt
+    # shards, or FEC_LOCATE_UNKNOWN per block; present_out and counts as for rs_locate, the masks with
+    # every located shard's bit cleared.
+    def rs_locate_multi_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, max_bad, bad_count,
+                            present_out=None, mask_words=None, counts=None, flags=FEC_DEVICE):
+        return lib.fec_rs_locate_multi_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, max_bad,
+                                             bad_count, present_out,
+                                             (k + m + 31) // 32 if mask_words is None else mask_words, counts, flags)
+
+    def _locate_multi(self, k, m, lay, max_bad, bad_count, present_out, counts, shard_len):
+        pa, W = (None, None) if present_out is None else self._col_masks(present_out, lay.B)
+        ca = None if counts is None else self._words_addr(counts, 2, "counts")
+        return _check(self.rs_locate_multi_raw(k, m, *lay.args(shard_len), max_bad,
+                                               self._words_addr(bad_count, lay.B, "bad_count"), pa, W, ca),
+                      "fec_rs_locate_multi_batch")
+
+    def rs_locate_multi(self, k, m, shards, bad_count, max_bad=FEC_LOCATE_MAX_BAD, present_out=None, counts=None,
+                        shard_len=None):
+        return self._locate_multi(k, m, _Layout(k, m, shards, None, _SOME), max_bad, bad_count, present_out, counts,
+                                  shard_len)
+
+    def rs_locate_multi_split(self, k, m, data, parity, bad_count, max_bad=FEC_LOCATE_MAX_BAD, present_out=None,
+                              counts=None, shard_len=None):
+        return self._locate_multi(k, m, _Layout(k, m, data, parity, _SOME), max_bad, bad_count, present_out, counts,
+                                  shard_len)
 
     def _reconstruct_some(self, k, m, lay, masks, want, status, shard_len):
         wa = None if want is None else self._words_addr(want, lay.B, "want")

@@ -14,6 +14,7 @@
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
+#include "fec_locate_multi.hpp"
 #include "gf256.h"
 #include "rs_matrix.hpp"
 
@@ -140,6 +141,20 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             }
             HIP_TRY(hipMalloc(&c.d_loc_carry, carry.size() * 4));
             HIP_TRY(hipMemcpy(c.d_loc_carry, carry.data(), carry.size() * 4, hipMemcpyHostToDevice));
+        }
+        if (m >= 1 && m <= fk::kLocateMultiRows) {
+            // the locate-multi call's coefficients as PermTabs, then the field's tables
+            // (fec_locate_multi.hpp)
+            uint8_t A[fk::kLocateMultiRows * fk::kLocateMultiRows];
+            fk::locate_multi_table(A, (uint32_t)k, (uint32_t)m);
+            std::vector<uint32_t> lm(fk::locate_multi_tab_words((uint32_t)m), 0);
+            for (int i = 0; i < m * m; ++i) {
+                const gf::PermTab t = gf::make_permtab(A[i]);
+                memcpy(&lm[(size_t)i * 8], &t, sizeof(t));
+            }
+            memcpy(&lm[(size_t)m * m * 8], &gf::kTables, sizeof(gf::Tables));
+            HIP_TRY(hipMalloc(&c.d_lmtab, lm.size() * 4));
+            HIP_TRY(hipMemcpy(c.d_lmtab, lm.data(), lm.size() * 4, hipMemcpyHostToDevice));
         }
         const std::vector<uint8_t> leaves = dyadic_leaves(c.matrix, k, m);
         if (!leaves.empty() && leaves.size() <= (size_t)m * k) {   // staged like m x k tables
@@ -300,6 +315,7 @@ void fec_ctx_destroy(fec_ctx* ctx) {
         if (kv.second.d_dall) (void)hipFree(kv.second.d_dall);
         if (kv.second.d_loctab) (void)hipFree(kv.second.d_loctab);
         if (kv.second.d_loc_carry) (void)hipFree(kv.second.d_loc_carry);
+        if (kv.second.d_lmtab) (void)hipFree(kv.second.d_lmtab);
     }
     if (ctx->own) (void)hipStreamSynchronize(ctx->own);
     if (ctx->stream && ctx->stream != ctx->own) (void)hipStreamSynchronize(ctx->stream);
@@ -433,7 +449,8 @@ int fec_rs_prepare(fec_ctx* ctx, int k, int m) {
 }
 
 // The argument checks every batch call makes before it runs, in the documented order (fec_hip.h):
-// shard counts, flags, shard_len, out_slots and mask_words; then the ctx and the code; an empty
+// shard counts (and the locate-multi call's limit on m), flags, shard_len, out_slots, max_bad and
+// mask_words; then the ctx and the code; an empty
 // call; null pointers; and for FEC_DEVICE the layout of the data, parity and out regions, in that
 // order, then the alignment of the word arrays. An entry point describes itself in a Call and gets
 // kRun back when it has work to do, else the code to return.
@@ -457,6 +474,8 @@ struct Call {
     bool wide = false;         // wide calls: words per present mask
     size_t mask_words = 1;
     int mask_n = 0;            // the shards a mask covers (0: k + m; the update calls' column masks: k)
+    int max_m = -1;            // the call's largest m (-1: none; the locate-multi call: 16)
+    int max_bad = 1;           // the locate-multi call's max_bad, in [1, FEC_LOCATE_MAX_BAD]
     struct {
         const void *a, *b;
     } words[2] = {};           // (mask, status)-like pairs of 4-byte arrays, either may be null
@@ -466,10 +485,12 @@ constexpr int kRun = 1;
 static int check_call(fec_ctx* ctx, const Call& c, Code** code) {
     if (c.k <= 0 || c.m < 0) return FEC_ERR_INV_SHARD_NUM;
     if (c.k + c.m > c.max_n) return FEC_ERR_MAX_SHARD_NUM;
+    if (c.max_m >= 0 && c.m > c.max_m) return FEC_ERR_INVALID_ARG;
     if (c.flags != FEC_DEVICE && !(c.host_ok && (c.flags == FEC_HOST || c.flags == FEC_HOST_PINNED)))
         return FEC_ERR_INVALID_ARG;
     if (c.len == 0) return FEC_ERR_SHARD_NO_DATA;
     if (c.len > (size_t(1) << 30) || c.out_slots <= 0) return FEC_ERR_INVALID_ARG;
+    if (c.max_bad < 1 || c.max_bad > FEC_LOCATE_MAX_BAD) return FEC_ERR_INVALID_ARG;
     if (c.wide && (c.mask_words < (size_t)FEC_MASK_WORDS(c.mask_n ? c.mask_n : c.k + c.m) || c.mask_words > 8))
         return FEC_ERR_INVALID_ARG;
     int rc = select_device(ctx);
@@ -641,6 +662,26 @@ int fec_rs_locate_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nbl
     return rs_locate_device(ctx, code, shard_len, nblocks,
                             {data, data_block_stride, parity, parity_block_stride, shard_stride, bad_shard,
                              present_out, mask_words, counts});
+}
+
+// Up to m/2 corrupt shards per block; m <= 16 (one pass of the scan's 16 rows).
+int fec_rs_locate_multi_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
+                              size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                              size_t shard_stride, int max_bad, int32_t* bad_count, uint32_t* present_out,
+                              size_t mask_words, uint32_t* counts, int flags) {
+    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &parity, parity_block_stride,
+           shard_stride};
+    c.null_arg = !bad_count;
+    c.max_m = fk::kLocateMultiRows, c.max_bad = max_bad;
+    c.wide = true, c.mask_words = mask_words;
+    c.words[0] = {present_out, bad_count};
+    c.words[1] = {counts, nullptr};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_locate_multi_device(ctx, code, shard_len, nblocks,
+                                  {data, data_block_stride, parity, parity_block_stride, shard_stride, max_bad,
+                                   bad_count, present_out, mask_words, counts});
 }
 
 // ---------------------------------------------------------------- update, encode-idx

@@ -1,11 +1,14 @@
 // fec_cores.cpp — the device-memory cores of the C ABI (fec_ctx.hpp): each cuts one call over device
 // memory into launches and fills their arguments. The FEC_DEVICE entry points (fec_capi.cpp) call
 // them on the caller's regions, the host-resident drivers (fec_host.cpp) on their staging buffers.
+#include <string.h>
+
 #include <algorithm>
 
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
+#include "fec_locate_multi.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
 #include "fec_update.hpp"
@@ -404,6 +407,89 @@ int rs_locate_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks,
         });
 }
 
+// Locate-multi (fec_locate_multi.hip; LocateMultiCall, fec_ctx.hpp). A batch is cut as the encode
+// cuts it (kMaxItems items per slice), and so that a slice's workspace (locate_multi_ws_bytes: one
+// bitmap bit per item, words + 1 words per block) stays under kPlanBytes.
+static size_t locate_multi_per_launch(size_t nblocks, uint32_t cps, uint32_t words) {
+    const size_t per_block = (size_t)(words + 1) * 4 + (cps + 7) / 8;   // (+ 47 bytes of rounding per slice)
+    return std::max<size_t>(1, std::min(blocks_per_launch(nblocks, cps), (kPlanBytes - 64) / per_block));
+}
+
+// What one slice of a locate-multi call runs, in order: `clear` bytes of the workspace set to zero, the
+// scan, the solve, the finalize.
+struct LocateMultiSlice {
+    size_t clear;
+    fk::LocateMultiScanArgs scan;
+    fk::LocateMultiSolveArgs solve;
+    fk::LocateMultiFinArgs fin;
+};
+
+// run(slice) for every slice of a call whose workspace is at ws, until one fails. No device work
+// (fec__selftest_locate_multi_slices calls it without one).
+template <class R>
+static int locate_multi_launches(const Code* code, size_t len, size_t nblocks, const LocateMultiCall& c, uint8_t* ws,
+                                 R run) {
+    const uint32_t cps = chunks_of(len);
+    const uint32_t n = (uint32_t)(code->k + code->m), words = (n + 31) / 32;
+    const uint32_t T = fk::locate_multi_radius((uint32_t)code->m, (uint32_t)c.max_bad);
+    return for_slices(nblocks, locate_multi_per_launch(nblocks, cps, words), [&](size_t b0, size_t nb) -> int {
+        LocateMultiSlice sl{};
+        sl.clear = fk::locate_multi_ws_bytes(nb, cps, words);
+        fk::LocateMultiScanArgs& a = sl.scan;
+        a.in = c.data + b0 * c.dbs;
+        a.par = c.parity + b0 * c.pbs;
+        a.in_bs = c.dbs;
+        a.par_bs = c.pbs;
+        a.ss = c.ss;
+        a.k = (uint32_t)code->k;
+        a.m = (uint32_t)code->m;
+        a.len = (uint32_t)len;
+        a.cps = cps;
+        a.total = (uint32_t)(nb * cps);
+        a.div_cps = fk::make_fastdiv(cps);
+        a.tabs = code->d_tabs;
+        a.bitmap = (uint64_t*)ws;
+        fk::LocateMultiSolveArgs& v = sl.solve;
+        v.s = a;
+        v.nwords = (uint32_t)(fk::locate_multi_bitmap_bytes((uint64_t)nb * cps) / sizeof(uint64_t));
+        v.n = n;
+        v.T = T;
+        v.words = words;
+        v.atabs = code->d_lmtab;
+        v.ft = code->d_lmtab ? (const uint8_t*)(code->d_lmtab + (size_t)code->m * code->m * 8) : nullptr;   // (m = 0)
+        v.blk = (uint32_t*)(ws + fk::locate_multi_bitmap_bytes((uint64_t)nb * cps));
+        fk::LocateMultiFinArgs& f = sl.fin;
+        f.blk = v.blk;
+        f.bad_count = c.bad_count + b0;
+        f.present = c.present ? c.present + b0 * c.mask_words : nullptr;
+        f.counts = c.counts;
+        f.nblocks = (uint32_t)nb;
+        f.n = n;
+        f.T = T;
+        f.words = words;
+        f.mask_words = (uint32_t)c.mask_words;
+        return run(sl);
+    });
+}
+
+// The counts are set to 0 on the stream, as verify presets its count; each slice clears its workspace,
+// which is the stream's (ctx->work), so slices and calls on one stream follow one another in it.
+int rs_locate_multi_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateMultiCall& c) {
+    const uint32_t cps = chunks_of(len);
+    const uint32_t words = (uint32_t)(code->k + code->m + 31) / 32;
+    const size_t per = locate_multi_per_launch(nblocks, cps, words);
+    const int rc = grow_plans(ctx, fk::locate_multi_ws_bytes(per, cps, words));
+    if (rc) return rc;
+    if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 2 * sizeof(uint32_t), ctx->stream));
+    return locate_multi_launches(code, len, nblocks, c, ctx->work->d_plans, [&](const LocateMultiSlice& sl) -> int {
+        HIP_TRY(hipMemsetAsync(ctx->work->d_plans, 0, sl.clear, ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_multi_scan(sl.scan, flat_grid(sl.scan.total), ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_multi_solve(sl.solve, ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_multi_finalize(sl.fin, ctx->stream));
+        return FEC_OK;
+    });
+}
+
 // Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
 // the wide tile, storing into both regions.
 int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
@@ -704,6 +790,88 @@ int fec__selftest_locate_slices(void) {
         if ((uintptr_t)got[p].tabs0 != car0 + (p - 1) * 16 * 130 * 8 * 4 ||
             (uintptr_t)got[p].tabs != (uintptr_t)got[p].tabs0 + 130 * 8 * 4)
             return 5;
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the slices of a locate-multi call
+// that the limits cut, for (k, m) = (5, 4), (5, 16), (5, 1), (5, 0) and (40, 16) (two mask words).
+// 70 000-byte shards (4375 chunks): a slice's workspace holds one bitmap bit per item and words + 1
+// words per block, and kPlanBytes of it are fewer blocks than kMaxItems items are, so a batch of one
+// block more than that has two slices. Every slice's clear size, data, parity and output bases, item
+// count, bitmap and block-word pointers, word count, radius and tables are compared with values worked
+// out here from the call's strides. Then 16-byte shards, where kMaxItems cuts nothing and the
+// workspace alone does. 0 on success, else 1000 * (code index + 1) + 100 * slice + the failing field.
+int fec__selftest_locate_multi_slices(void) {
+    const size_t L = 70000, cps = 4375, W = 3;
+    const size_t ss = 70016;
+    const uintptr_t in0 = uintptr_t(1) << 40, par0 = uintptr_t(3) << 40, mask0 = uintptr_t(4) << 40,
+                    tab0 = uintptr_t(5) << 40, cnt0 = uintptr_t(6) << 40, out0 = uintptr_t(7) << 40,
+                    lm0 = uintptr_t(8) << 40, ws0 = uintptr_t(9) << 40;
+    static const int codes[][3] = {{5, 4, 8}, {5, 16, 3}, {5, 1, 1}, {5, 0, 2}, {40, 16, 8}};   // k, m, max_bad
+    static const uint32_t want_T[] = {2, 3, 0, 0, 8};
+    int ci = 0;
+    for (auto& cd : codes) {
+        const int base = 1000 * ++ci;
+        const int k = cd[0], m = cd[1];
+        const size_t words = (size_t)(k + m + 31) / 32;
+        const size_t per = std::min<size_t>(kMaxItems / cps, (kPlanBytes - 64) / ((words + 1) * 4 + (cps + 7) / 8));
+        const size_t B = per + 1, dbs = k * ss + 48, pbs = (size_t)m * ss + 32;
+        if (per >= (size_t)(kMaxItems / cps)) return base + 1;   // the workspace is the tighter limit here
+        Code code;
+        code.k = k;
+        code.m = m;
+        code.d_tabs = (uint32_t*)tab0;
+        code.d_lmtab = (uint32_t*)lm0;
+        const LocateMultiCall c{(const uint8_t*)in0, dbs, (const uint8_t*)par0, pbs, ss, cd[2], (int32_t*)out0,
+                                (uint32_t*)mask0, W, (uint32_t*)cnt0};
+        std::vector<LocateMultiSlice> got;
+        const int rc = locate_multi_launches(&code, L, B, c, (uint8_t*)ws0, [&](const LocateMultiSlice& sl) -> int {
+            got.push_back(sl);
+            return FEC_OK;
+        });
+        code.d_tabs = code.d_lmtab = nullptr;
+        if (rc != FEC_OK || got.size() != 2) return base + 2;
+        for (size_t s = 0; s < 2; ++s) {
+            const LocateMultiSlice& sl = got[s];
+            const int fail = base + 100 * (int)s;
+            const size_t b0 = s * per, nb = s ? 1 : per;
+            const size_t bm = (nb * cps + 255) / 256 * 32, bw = (nb * (words + 1) * 4 + 15) / 16 * 16;
+            if (sl.clear != bm + bw || sl.clear > kPlanBytes) return fail + 3;
+            const fk::LocateMultiScanArgs& a = sl.scan;
+            if ((uintptr_t)a.in != in0 + b0 * dbs || a.in_bs != dbs || a.ss != ss) return fail + 4;
+            if ((uintptr_t)a.par != par0 + b0 * pbs || a.par_bs != pbs) return fail + 5;
+            if (a.k != (uint32_t)k || a.m != (uint32_t)m || a.len != L || a.cps != cps) return fail + 6;
+            if (a.total != nb * cps || a.div_cps.d != cps) return fail + 7;
+            if ((uintptr_t)a.tabs != tab0 || (uintptr_t)a.bitmap != ws0) return fail + 8;
+            const fk::LocateMultiSolveArgs& v = sl.solve;
+            if (memcmp(&v.s, &a, sizeof(a)) != 0) return fail + 9;
+            if (v.nwords != bm / 8 || v.n != (uint32_t)(k + m) || v.T != want_T[ci - 1] || v.words != words)
+                return fail + 10;
+            if ((uintptr_t)v.atabs != lm0 || (uintptr_t)v.ft != lm0 + (size_t)m * m * 32) return fail + 11;
+            if ((uintptr_t)v.blk != ws0 + bm) return fail + 12;
+            const fk::LocateMultiFinArgs& f = sl.fin;
+            if ((uintptr_t)f.blk != ws0 + bm || (uintptr_t)f.bad_count != out0 + b0 * 4) return fail + 13;
+            if ((uintptr_t)f.present != mask0 + b0 * W * 4 || f.mask_words != W) return fail + 14;
+            if ((uintptr_t)f.counts != cnt0 || f.nblocks != nb || f.n != v.n || f.T != v.T || f.words != words)
+                return fail + 15;
+        }
+    }
+    // no masks and no counts asked for: none in any finalize; 16-byte shards: 2^31 items fit a launch
+    // but their workspace does not (10 bytes a block)
+    Code code;
+    code.k = 5;
+    code.m = 4;
+    const LocateMultiCall c{(const uint8_t*)in0, 128, (const uint8_t*)par0, 64, 16, 1, (int32_t*)out0, nullptr, 1, nullptr};
+    const size_t per = (kPlanBytes - 64) / 9, B = 2 * per + 5;
+    size_t slices = 0, blocks = 0;
+    int bad = 0;
+    (void)locate_multi_launches(&code, 16, B, c, (uint8_t*)ws0, [&](const LocateMultiSlice& sl) -> int {
+        if (sl.fin.present || sl.fin.counts || sl.solve.T != 1 || sl.clear > kPlanBytes) ++bad;
+        if (sl.scan.total != sl.fin.nblocks || (uintptr_t)sl.scan.in != in0 + blocks * 128) ++bad;
+        ++slices, blocks += sl.fin.nblocks;
+        return FEC_OK;
+    });
+    if (bad || slices != 3 || blocks != B) return 3;
     return 0;
 }
 

@@ -26,6 +26,7 @@ struct Code {
     uint8_t* d_dall = nullptr;     // n bytes: sum_{t != s} log(s ^ t) mod 255 (sorted plans)
     uint8_t* d_loctab = nullptr;   // m > 0: the locate call's table (fec_locate.hpp locate_table)
     uint32_t* d_loc_carry = nullptr;   // k > 128, m > 16: PermTabs of locate's later passes, a slab per pass
+    uint32_t* d_lmtab = nullptr;   // 1 <= m <= 16: the locate-multi call's table (fec_locate_multi.hpp)
 };
 
 // Bytes of staged shards per FEC_HOST chunk (x2 buffers, in and out).
@@ -167,6 +168,20 @@ struct LocateCall {
     uint32_t* counts;
 };
 int rs_locate_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateCall& c);
+// Locate-multi (fec_locate_multi.hip): the regions and outputs of one call (present and counts may be
+// null), m <= 16.
+struct LocateMultiCall {
+    const uint8_t* data;
+    size_t dbs;
+    const uint8_t* parity;
+    size_t pbs, ss;
+    int max_bad;
+    int32_t* bad_count;
+    uint32_t* present;
+    size_t mask_words;
+    uint32_t* counts;
+};
+int rs_locate_multi_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateMultiCall& c);
 int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
                                uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, const uint32_t* want,
                                int32_t* status, int* err);

@@ -10,6 +10,7 @@
 #include "../../include/fec_hip.h"
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
+#include "fec_locate_multi.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
 #include "fec_wide.hpp"
@@ -316,6 +317,220 @@ int fec__selftest_locate(void) {
     if (fk::locate_merge(7, CL) != 7 || fk::locate_merge(7, 7) != 7 || fk::locate_merge(7, 8) != UN) return 2;
     if (fk::locate_merge(7, UN) != UN || fk::locate_merge(UN, CL) != UN || fk::locate_merge(UN, 7) != UN) return 3;
     if (fk::locate_merge(UN, UN) != UN || fk::locate_merge(0, 255) != UN || fk::locate_merge(0, 0) != 0) return 4;
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the locate-multi call's
+// arithmetic (fec_locate_multi.hpp: locate_multi_table, locate_multi_chunk with its column solver,
+// locate_multi_count, the functions the solve and finalize kernels run) against the brute-force
+// definition, on syndromes. Per code and per max_bad = 1 .. 8 (T = min(max_bad, m / 2)): seeded blocks
+// of three 16-byte chunks in fourteen error patterns (none; one byte; T shards in one byte column; T
+// shards each in another chunk; supports {a,b} and {b,c} in two chunks; shard 0 among the corrupt;
+// parity shards only; a data and a parity shard; one shard, every byte; T + 1 shards in one column;
+// T + 1 shards spread so that no chunk holds more than T; t random shards, 0 <= t <= n; t random
+// shards, T < t <= m - T; up to T shards with several bytes each). The syndromes are those of the
+// errors under the code's own matrix; the chunks are solved one by one, their supports ORed, and the
+// result must be
+//   - where the subsets can be counted (n <= 12, and RS(16,24) at max_bad <= 2): what the definition
+//     gives, by trying every set of at most T shards in ascending size and asking whether every
+//     syndrome column lies in the span of those columns of [P | I] (at most one set of the smallest
+//     size may pass);
+//   - everywhere: exactly the t corrupt shards if t <= T, unknown if T < t <= m - T.
+// With max_bad = 1 the result must also agree with locate_chunk / locate_merge (fec_locate.hpp). 0 on
+// success, else 100000 * (code index + 1) + 1000 * max_bad + case index + 1.
+int fec__selftest_locate_multi(void) {
+    static const int shapes[][2] = {{1, 2},  {2, 2},   {6, 3},  {3, 5},    {8, 4},  {1, 8},
+                                    {16, 8}, {20, 10}, {4, 16}, {240, 16}, {31, 1}, {32, 0}};
+    constexpr int R = fk::kLocateMultiRows;
+    constexpr uint32_t C = 3, W = 16 * C, NW = fk::kLocateMultiWords;
+    uint64_t seed = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    auto nzbyte = [&rnd]() -> uint8_t { return (uint8_t)(1 + rnd() % 255); };
+    const uint8_t* ft = reinterpret_cast<const uint8_t*>(&gf::kTables);
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix((int)k, (int)n);
+        if (M.empty()) return 100000 * si;
+        const uint8_t* P = M.data() + (size_t)k * k;   // parity rows
+        uint8_t A[R * R] = {};
+        fk::locate_multi_table(A, k, m);
+        std::vector<gf::PermTab> At((size_t)m * m), Tp((size_t)m * k);
+        for (size_t i = 0; i < At.size(); ++i) At[i] = gf::make_permtab(A[i]);
+        for (size_t i = 0; i < Tp.size(); ++i) Tp[i] = gf::make_permtab(P[i]);
+        uint8_t loctab[fk::kLocateTabBytes];
+        if (m && !fk::locate_table(loctab, P, k, m)) return 100000 * si;
+        // column r of [P | I]
+        auto col = [&](uint32_t r, uint32_t i) -> uint8_t { return r < k ? P[i * k + r] : (uint8_t)(r - k == i); };
+
+        for (uint32_t max_bad = 1; max_bad <= (uint32_t)fk::kLocateMaxBad; ++max_bad) {
+            const uint32_t T = fk::locate_multi_radius(m, max_bad);
+            if (T != std::min(max_bad, m / 2)) return 100000 * si + 1000 * (int)max_bad;
+            const bool brute = n <= 12 || (k == 16 && m == 8 && max_bad <= 2);
+            for (int ci = 0; ci < 14 * 3; ++ci) {
+                const int fail = 100000 * si + 1000 * (int)max_bad + ci + 1;
+                std::vector<uint8_t> S((size_t)m * W, 0);
+                std::vector<uint8_t> hit(n, 0);
+                auto err = [&](uint32_t r, uint32_t x, uint8_t e) {   // shard r, byte x ^= e: a second error of
+                    if (hit[r] & (1u << (x / 16))) return;            // a shard stays out of a chunk it is in
+                    hit[r] |= (uint8_t)(1u << (x / 16));
+                    for (uint32_t i = 0; i < m; ++i) S[i * W + x] ^= gf::mul(col(r, i), e);
+                };
+                std::vector<uint32_t> perm(n);   // distinct random shards: perm[0], perm[1], ...
+                for (uint32_t r = 0; r < n; ++r) perm[r] = r;
+                for (uint32_t r = 0; r + 1 < n; ++r) std::swap(perm[r], perm[r + rnd() % (n - r)]);
+                const uint32_t x0 = rnd() % 16, x1 = 16 + rnd() % 16;
+                auto some = [&](uint32_t t) { return std::min(t, n); };
+                switch (ci % 14) {
+                    case 0: break;
+                    case 1: err(perm[0], rnd() % W, (uint8_t)(1u << (rnd() % 8))); break;
+                    case 2:
+                        for (uint32_t i = 0; i < some(T); ++i) err(perm[i], x1, nzbyte());
+                        break;
+                    case 3:
+                        for (uint32_t i = 0; i < some(T); ++i) err(perm[i], 16 * (i % C) + rnd() % 16, nzbyte());
+                        break;
+                    case 4:
+                        err(perm[0], x0, nzbyte());
+                        if (n > 1) err(perm[1], x0, nzbyte()), err(perm[1], x1, nzbyte());
+                        if (n > 2) err(perm[2], x1, nzbyte());
+                        break;
+                    case 5:
+                        err(0, x1, nzbyte());
+                        for (uint32_t i = 0, left = T ? T - 1 : 0; i < n && left; ++i)
+                            if (perm[i] != 0) err(perm[i], x1, nzbyte()), --left;
+                        break;
+                    case 6:
+                        for (uint32_t i = 0; i < std::min(std::max(T, 1u), m); ++i) err(k + (perm[0] + i) % m, x0, nzbyte());
+                        break;
+                    case 7:
+                        err(rnd() % k, x0, nzbyte());
+                        if (m) err(k + rnd() % m, x1, nzbyte());
+                        break;
+                    case 8:
+                        for (uint32_t x = 0; x < W; ++x) err(perm[0], x, nzbyte()), hit[perm[0]] = 0;
+                        hit[perm[0]] = 7;
+                        break;
+                    case 9:
+                        for (uint32_t i = 0; i < some(T + 1); ++i) err(perm[i], x0, nzbyte());
+                        break;
+                    case 10:
+                        for (uint32_t i = 0; i < some(T + 1); ++i) err(perm[i], 16 * (i % C) + x0, nzbyte());
+                        break;
+                    case 11:
+                        for (uint32_t i = 0, t = rnd() % (n + 1); i < t; ++i) err(perm[i], rnd() % W, nzbyte());
+                        break;
+                    case 12:
+                        if (m >= 2 * T + 1)
+                            for (uint32_t i = 0, t = T + 1 + rnd() % (m - 2 * T); i < some(t); ++i)
+                                err(perm[i], x1, nzbyte());
+                        break;
+                    default:
+                        for (uint32_t i = 0, t = T ? 1 + rnd() % T : 0; i < some(t); ++i)
+                            for (uint32_t c = 0; c < C; ++c) err(perm[i], 16 * c + rnd() % 16, nzbyte());
+                }
+                uint32_t t = 0;
+                uint32_t hitset[NW] = {};
+                for (uint32_t r = 0; r < n; ++r)
+                    if (hit[r]) ++t, hitset[r >> 5] |= 1u << (r & 31u);
+
+                // the code under test: chunk by chunk, supports ORed, then the count
+                uint32_t sup[NW] = {};
+                bool unknown = false;
+                for (uint32_t c = 0; c < C; ++c) {
+                    uint32_t acc[R][4] = {};
+                    for (uint32_t i = 0; i < m; ++i) memcpy(acc[i], &S[i * W + 16 * c], 16);
+                    uint32_t cs[NW] = {};
+                    if (fk::locate_multi_chunk<R>(acc, m, n, T, At.data(), ft, cs)) unknown = true;
+                    for (uint32_t w = 0; w < NW; ++w) sup[w] |= cs[w];
+                }
+                const int32_t got = fk::locate_multi_count(sup, NW, unknown, T);
+                const bool any = std::any_of(S.begin(), S.end(), [](uint8_t v) { return v != 0; });
+                if ((got == 0) != !any) return fail;
+
+                // the two guarantees
+                if (t <= T && (got != (int32_t)t || memcmp(sup, hitset, sizeof(sup)) != 0)) return fail;
+                if (t > T && t + T <= m && got != fk::kLocateUnknown) return fail;
+
+                // the definition
+                if (brute) {
+                    int32_t want = fk::kLocateUnknown;
+                    uint32_t wantset[NW] = {};
+                    for (uint32_t v = 0; v <= T && want == fk::kLocateUnknown; ++v) {
+                        std::vector<uint32_t> idx(v);   // combinations of v shards, ascending
+                        for (uint32_t i = 0; i < v; ++i) idx[i] = i;
+                        int found = 0;
+                        for (bool more = v <= n; more;) {
+                            // [H_E | S] reduced on H_E's columns; rows without a pivot must be zero in S
+                            std::vector<uint8_t> G((size_t)m * (v + W));
+                            for (uint32_t i = 0; i < m; ++i) {
+                                for (uint32_t j = 0; j < v; ++j) G[i * (v + W) + j] = col(idx[j], i);
+                                memcpy(&G[i * (v + W) + v], &S[i * W], W);
+                            }
+                            uint32_t row = 0;
+                            for (uint32_t j = 0; j < v && row < m; ++j) {
+                                uint32_t p = row;
+                                while (p < m && G[p * (v + W) + j] == 0) ++p;
+                                if (p == m) continue;
+                                for (uint32_t x = 0; x < v + W; ++x) std::swap(G[p * (v + W) + x], G[row * (v + W) + x]);
+                                const uint8_t pi = gf::inv(G[row * (v + W) + j]);
+                                for (uint32_t i = row + 1; i < m; ++i) {
+                                    const uint8_t f = gf::mul(G[i * (v + W) + j], pi);
+                                    if (f)
+                                        for (uint32_t x = j; x < v + W; ++x)
+                                            G[i * (v + W) + x] ^= gf::mul(f, G[row * (v + W) + x]);
+                                }
+                                ++row;
+                            }
+                            bool ok = true;
+                            for (uint32_t i = row; i < m && ok; ++i)
+                                for (uint32_t x = v; x < v + W; ++x) ok = ok && G[i * (v + W) + x] == 0;
+                            if (ok) {
+                                ++found, want = (int32_t)v;
+                                memset(wantset, 0, sizeof(wantset));
+                                for (uint32_t j = 0; j < v; ++j) wantset[idx[j] >> 5] |= 1u << (idx[j] & 31u);
+                            }
+                            // the next combination
+                            more = false;
+                            for (uint32_t i = v; i-- > 0;)
+                                if (idx[i] < n - v + i) {
+                                    ++idx[i];
+                                    for (uint32_t j = i + 1; j < v; ++j) idx[j] = idx[j - 1] + 1;
+                                    more = true;
+                                    break;
+                                }
+                        }
+                        if (found > 1) return fail;   // (distance m + 1 > 2 T rules it out)
+                    }
+                    if (got != want) return fail;
+                    if (want > 0 && memcmp(sup, wantset, sizeof(sup)) != 0) return fail;
+                }
+
+                // max_bad = 1 against the single-shard call's classifier and merge
+                if (max_bad == 1) {
+                    int32_t word = fk::kLocateClean;
+                    for (uint32_t c = 0; m > 0 && c < C; ++c) {
+                        uint32_t acc[R][4] = {};
+                        for (uint32_t i = 0; i < m; ++i) memcpy(acc[i], &S[i * W + 16 * c], 16);
+                        word = fk::locate_merge(word, fk::locate_chunk<R>(acc, m, 1, k, m, Tp.data(), loctab, word));
+                    }
+                    if (word == fk::kLocateClean && got != 0) return fail;
+                    if (word == fk::kLocateUnknown && got != fk::kLocateUnknown) return fail;
+                    if (word >= 0) {
+                        uint32_t one[NW] = {};
+                        one[word >> 5] = 1u << (word & 31);
+                        if (got != 1 || memcmp(sup, one, sizeof(sup)) != 0) return fail;
+                    }
+                }
+            }
+        }
+    }
     return 0;
 }
 

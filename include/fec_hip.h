@@ -28,6 +28,8 @@
  *   fec_rs_locate_batch         no counterpart: which shard of a block that fails Verify is the corrupt
  *                               one (klauspost's advice is to leave out each shard in turn, reconstruct
  *                               and verify again), and the present mask that heals the block
+ *   fec_rs_locate_multi_batch   no counterpart: up to m/2 corrupt shards of a block that fails Verify, the
+ *                               radius of the code, and the present mask that heals the block (m <= 16)
  *   fec_rs_reconstruct_some_batch
  *                               Encoder.Reconstruct (want_mask NULL) and Encoder.ReconstructSome, in
  *                               place: missing parity shards are rebuilt too (klauspost's interface;
@@ -328,7 +330,9 @@ int fec_rs_verify_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
  *
  * Cost. A clean batch is read once per pass and no atomic is issued, as by fec_rs_verify_batch; a
  * pass takes parity row 0 and 15 further rows (verify: 16 rows), so codes of m > 16 read row 0 again
- * in each pass and some of them (m = 32, 47, 48, ...) take one pass more than verify. */
+ * in each pass and some of them (m = 32, 47, 48, ...) take one pass more than verify.
+ *
+ * fec_rs_locate_multi_batch (below) names up to m / 2 corrupt shards of a block. */
 #define FEC_LOCATE_CLEAN (-1)
 #define FEC_LOCATE_UNKNOWN (-2)
 int fec_rs_locate_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
@@ -337,6 +341,57 @@ int fec_rs_locate_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
                         size_t shard_stride, int32_t *bad_shard,
                         uint32_t *present_out, size_t mask_words,
                         uint32_t *counts, int flags);
+
+/* Locate up to m / 2 corrupt shards of a block that fails verify: fec_rs_locate_batch to the radius
+ * of the code, which has distance m + 1. Regions, layouts, alignment rules and FEC_DEVICE-only are
+ * those of fec_rs_locate_batch: all k + m shards of a block are given and only bytes [0, shard_len)
+ * of each slot count.
+ *
+ * Let T = min(max_bad, m / 2). Per block b, let E_b be the smallest set of shards, |E_b| <= T, such
+ * that replacing bytes [0, shard_len) of the shards in E_b alone can make the block consistent. If
+ * such a set exists it is unique (two would differ by a nonzero codeword of weight <= 2 T <= m), and
+ * it is the union, over byte columns, of the supports of each column's unique error vector of weight
+ * <= T. bad_count[b] receives
+ *   0                   the block is consistent
+ *   |E_b| in [1, T]     E_b exists
+ *   FEC_LOCATE_UNKNOWN  otherwise; with m <= 1 (T = 0) every inconsistent block
+ * With m == 0 every block is 0. t corrupt shards with t <= T are always located exactly; with
+ * T < t <= m - T the block is always unknown; with t > m - T a wrong set can be named, as by any
+ * decoder past its distance. With max_bad == 1 the results agree with fec_rs_locate_batch block for
+ * block: clean with 0, shard s with count 1 and bit s cleared, unknown with unknown.
+ *
+ * Outputs, all device memory, 4-byte aligned (else FEC_ERR_ALIGNMENT); the call sets every word of
+ * each, the caller need not clear them:
+ *   bad_count    (required) nblocks results
+ *   present_out  (optional) nblocks x mask_words words in the wide calls' bit order: bits [0, k + m)
+ *                set, less the bits of E_b; an unknown block keeps all k + m bits, so that healing
+ *                leaves it untouched; bits at and above k + m zero. These are the masks that heal
+ *                through fec_rs_reconstruct_some_batch (k + m <= 32, mask_words == 1) or
+ *                fec_rs_reconstruct_wide_batch (which rebuilds data shards: a located parity shard is
+ *                then re-encoded). FEC_MASK_WORDS(k + m) <= mask_words <= 8, else
+ *                FEC_ERR_INVALID_ARG, whether or not present_out is given
+ *   counts       (optional) two uint32: when the call's work completes on the stream, [0] holds the
+ *                located blocks (count >= 1) and [1] the unknown ones
+ * Nothing else is written; a corrupt block is a result, not an error: the sticky word is untouched.
+ * The call is stream-ordered like its siblings; its scratch memory (one bit per 16-byte chunk column
+ * of a block and FEC_MASK_WORDS(k + m) + 1 words per block) is the ctx's workspace.
+ *
+ * Scope: k >= 1, 0 <= m <= 16, k + m <= 256. m > 16 is not yet supported and returns
+ * FEC_ERR_INVALID_ARG, checked right after k + m; max_bad outside [1, FEC_LOCATE_MAX_BAD] returns
+ * FEC_ERR_INVALID_ARG, checked after shard_len and before mask_words. The other host-side checks come
+ * in fec_rs_locate_batch's order.
+ *
+ * Cost. A clean batch is read once, no atomic is issued and nothing is written but the outputs; a
+ * bitmap clear and one launch over the bitmap come on top of fec_rs_locate_batch's work. Only the
+ * chunks that hold a nonzero syndrome are read again and solved, one lane per chunk: a batch with
+ * many corrupt chunks takes several times fec_rs_locate_batch's time. */
+#define FEC_LOCATE_MAX_BAD 8
+int fec_rs_locate_multi_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                              const uint8_t *data, size_t data_block_stride,
+                              const uint8_t *parity, size_t parity_block_stride,
+                              size_t shard_stride, int max_bad, int32_t *bad_count,
+                              uint32_t *present_out, size_t mask_words,
+                              uint32_t *counts, int flags);
 
 /* RS Reconstruct / ReconstructSome, in place: as fec_rs_reconstruct_batch (k + m <=
  * FEC_MAX_DECODE_SHARDS, one uint32 present mask per block), but missing PARITY shards are rebuilt
