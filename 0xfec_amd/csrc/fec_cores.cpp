@@ -53,6 +53,27 @@ static void fill_row_pass(Args& a, const Code* code, int r0, const uint8_t* data
     a.tabs = code->d_tabs + (size_t)r0 * code->k * 8;
 }
 
+// The item fields of a flat launch over nb blocks of cps chunks each (shards of len bytes).
+template <class Args>
+static void fill_flat(Args& a, size_t len, uint32_t cps, size_t nb) {
+    a.len = (uint32_t)len;
+    a.cps = cps;
+    a.total = (uint32_t)(nb * cps);
+    a.div_cps = fk::make_fastdiv(cps);
+}
+
+// A launch that starts from the stored parity (SyndromeArgs; UpdateArgs; LocateArgs, which then sets
+// its own m and tables) over blocks [b0, b0 + nb) of a call: the row pass from r0, the parity from
+// that row, the item fields.
+template <class Args, class Par>
+static void fill_syndrome(Args& a, const Code* code, int r0, const uint8_t* data, size_t dbs, Par* parity,
+                          size_t pbs, size_t ss, size_t len, uint32_t cps, size_t b0, size_t nb) {
+    fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
+    a.par = parity + b0 * pbs + (size_t)r0 * ss;
+    a.par_bs = pbs;
+    fill_flat(a, len, cps, nb);
+}
+
 int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data,
                      size_t dbs, uint8_t* parity, size_t pbs, size_t ss) {
     const uint32_t cps = chunks_of(len);
@@ -63,10 +84,7 @@ int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const
             fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
             a.out = parity + b0 * pbs + (size_t)r0 * ss;
             a.out_bs = pbs;
-            a.len = (uint32_t)len;
-            a.cps = cps;
-            a.total = (uint32_t)(nb * cps);
-            a.div_cps = fk::make_fastdiv(cps);
+            fill_flat(a, len, cps, nb);
             a.dytabs = (r0 == 0 && (int)a.m == code->m) ? code->d_dytabs : nullptr;
             a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {data, dbs, ss, (uint64_t)k},
                                            {parity, pbs, ss, (uint64_t)code->m}, len, nblocks);
@@ -287,13 +305,7 @@ int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const
     return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
             fk::VerifyArgs a{};
-            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
-            a.par = parity + b0 * pbs + (size_t)r0 * ss;
-            a.par_bs = pbs;
-            a.len = (uint32_t)len;
-            a.cps = cps;
-            a.total = (uint32_t)(nb * cps);
-            a.div_cps = fk::make_fastdiv(cps);
+            fill_syndrome(a, code, r0, data, dbs, parity, pbs, ss, len, cps, b0, nb);
             a.status = status + b0;
             a.count = count;
             HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
@@ -307,17 +319,10 @@ int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const
 // from r0. No device work (fec__selftest_update_slices calls it without one).
 static void fill_update_launch(fk::UpdateArgs& a, const Code* code, int r0, size_t b0, size_t nb, size_t len,
                                const UpdateCall& u) {
-    const uint32_t cps = chunks_of(len);
-    fill_row_pass(a, code, r0, u.in + b0 * u.in_bs, u.in_bs, u.ss);
+    fill_syndrome(a, code, r0, u.in, u.in_bs, u.parity, u.pbs, u.ss, len, chunks_of(len), b0, nb);
     a.old = u.old ? u.old + b0 * u.old_bs : nullptr;
     a.old_bs = u.old_bs;
-    a.par = u.parity + b0 * u.pbs + (size_t)r0 * u.ss;
-    a.par_bs = u.pbs;
-    a.len = (uint32_t)len;
-    a.cps = cps;
-    a.total = (uint32_t)(nb * cps);
     a.nblocks = (uint32_t)nb;
-    a.div_cps = fk::make_fastdiv(cps);
     a.masks = u.masks + b0 * u.mask_words;
     a.mask_words = (uint32_t)u.mask_words;
 }
@@ -355,19 +360,10 @@ static int locate_launches(const Code* code, size_t len, size_t nblocks, const L
     return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
         for (int r0 = 1; code->m > 0 && (r0 == 1 || r0 < code->m); r0 += fk::kLocateRows - 1) {
             fk::LocateArgs a{};
-            a.in = c.data + b0 * c.dbs;
-            a.par = c.parity + b0 * c.pbs;
-            a.in_bs = c.dbs;
-            a.par_bs = c.pbs;
-            a.ss = c.ss;
-            a.k = (uint32_t)code->k;
+            fill_syndrome(a, code, 0, c.data, c.dbs, c.parity, c.pbs, c.ss, len, cps, b0, nb);
             a.m = (uint32_t)code->m;
             a.r0 = (uint32_t)r0;
             a.rows = 1u + (uint32_t)std::min(fk::kLocateRows - 1, code->m - r0);
-            a.len = (uint32_t)len;
-            a.cps = cps;
-            a.total = (uint32_t)(nb * cps);
-            a.div_cps = fk::make_fastdiv(cps);
             if (r0 > 1 && code->d_loc_carry) {   // the pass's slab: row 0's tables, then its rows'
                 a.tabs0 = code->d_loc_carry + (size_t)(r0 / (fk::kLocateRows - 1) - 1) * fk::kLocateRows * code->k * 8;
                 a.tabs = a.tabs0 + (size_t)code->k * 8;
@@ -436,18 +432,7 @@ static int locate_multi_launches(const Code* code, size_t len, size_t nblocks, c
         LocateMultiSlice sl{};
         sl.clear = fk::locate_multi_ws_bytes(nb, cps, words);
         fk::LocateMultiScanArgs& a = sl.scan;
-        a.in = c.data + b0 * c.dbs;
-        a.par = c.parity + b0 * c.pbs;
-        a.in_bs = c.dbs;
-        a.par_bs = c.pbs;
-        a.ss = c.ss;
-        a.k = (uint32_t)code->k;
-        a.m = (uint32_t)code->m;
-        a.len = (uint32_t)len;
-        a.cps = cps;
-        a.total = (uint32_t)(nb * cps);
-        a.div_cps = fk::make_fastdiv(cps);
-        a.tabs = code->d_tabs;
+        fill_syndrome(a, code, 0, c.data, c.dbs, c.parity, c.pbs, c.ss, len, cps, b0, nb);   // (m <= 16)
         a.bitmap = (uint64_t*)ws;
         fk::LocateMultiSolveArgs& v = sl.solve;
         v.s = a;
@@ -599,10 +584,7 @@ static fk::XorArgs xor_slice(int k, size_t len, uint32_t cps, const uint8_t* in,
     a.out_bs = out_bs;
     a.ss = ss;
     a.k = (uint32_t)k;
-    a.len = (uint32_t)len;
-    a.cps = cps;
-    a.total = (uint32_t)(nb * cps);
-    a.div_cps = fk::make_fastdiv(cps);
+    fill_flat(a, len, cps, nb);
     return a;
 }
 

@@ -3,7 +3,7 @@
 // stored parity and the data chunks fold through the code's PermTabs, so they end as the syndromes.
 // A lane whose syndromes are zero is done, as in verify; a lane that holds an anomaly classifies its
 // chunk (fec_locate.hpp locate_chunk) and the block's verdict word collects the proposals.
-#include "fec_device.hpp"
+#include "fec_flat.hpp"
 #include "fec_locate.hpp"
 
 namespace fk {
@@ -26,13 +26,8 @@ __global__ __launch_bounds__(kThreads) void rs_locate_kernel(LocateArgs a) {
         stage_tabs<true>(a.tabs, (rows - 1) * k * 8, smem + (size_t)k * sizeof(gf::PermTab));
         __syncthreads();
     }
-    // the grid is exactly the items' workgroups; a lane past the end repeats the last item and
-    // reports nothing, so every lane of a wave reaches the ballots below
-    const uint32_t item = xcd_order() * kThreads + threadIdx.x;
-    const bool live = item < a.total;
-    const uint32_t it = min(item, a.total - 1u);
-    const uint32_t b = fdiv(it, a.div_cps);
-    const uint32_t c = it - b * a.cps;
+    const FlatItem f = flat_item(a.total, a.cps, a.div_cps);
+    const uint32_t b = f.b, c = f.c;
     const uint8_t* src = a.in + (uint64_t)b * a.in_bs + (uint64_t)c * kChunk;
     const uint64_t poff = (uint64_t)b * a.par_bs + (uint64_t)c * kChunk;
     uint32_t acc[ROWS][4];
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(kThreads) void rs_locate_kernel(LocateArgs a) {
         if (r < (int)rows) d.x |= acc[r][0], d.y |= acc[r][1], d.z |= acc[r][2], d.w |= acc[r][3];
     const uint32_t nb = a.len - c * kChunk;
     d = keep_bytes(d, nb);
-    const bool bad = live && (d.x | d.y | d.z | d.w) != 0;
+    const bool bad = f.live && (d.x | d.y | d.z | d.w) != 0;
     uint64_t todo = __ballot(bad);   // wave-uniform
     if (todo == 0) return;
     int32_t prop = kLocateClean;

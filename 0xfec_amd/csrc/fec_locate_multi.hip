@@ -3,7 +3,7 @@
 // (fec_verify.hip) that ends in one bitmap word per wave, written only where a lane holds a nonzero
 // syndrome. The solve walks the bitmap and works on the flagged chunks alone (fec_locate_multi.hpp
 // locate_multi_chunk); the finalize turns each block's merged words into its outputs.
-#include "fec_device.hpp"
+#include "fec_flat.hpp"
 #include "fec_locate_multi.hpp"
 
 namespace fk {
@@ -16,14 +16,9 @@ __global__ __launch_bounds__(kThreads) void rs_locate_multi_scan_kernel(LocateMu
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const gf::PermTab* tabs = stage_tabs<LDS_TABS>(a.tabs, a.m * a.k * 8, smem);
     if constexpr (LDS_TABS) __syncthreads();
-    // the grid is exactly the items' workgroups; a lane past the end repeats the last item and
-    // reports nothing
     const uint32_t k = a.k, m = a.m;
-    const uint32_t item = xcd_order() * kThreads + threadIdx.x;
-    const bool live = item < a.total;
-    const uint32_t it = min(item, a.total - 1u);
-    const uint32_t b = fdiv(it, a.div_cps);
-    const uint32_t c = it - b * a.cps;
+    const FlatItem f = flat_item(a.total, a.cps, a.div_cps);
+    const uint32_t b = f.b, c = f.c;
     const uint8_t* src = a.in + (uint64_t)b * a.in_bs + (uint64_t)c * kChunk;
     const uint8_t* par = a.par + (uint64_t)b * a.par_bs + (uint64_t)c * kChunk;
     uint32_t acc[ROWS][4];
@@ -43,8 +38,8 @@ __global__ __launch_bounds__(kThreads) void rs_locate_multi_scan_kernel(LocateMu
     for (int r = 0; r < ROWS; ++r)
         if (r < (int)m) d.x |= acc[r][0], d.y |= acc[r][1], d.z |= acc[r][2], d.w |= acc[r][3];
     d = keep_bytes(d, a.len - c * kChunk);
-    const uint64_t flagged = __ballot(live && (d.x | d.y | d.z | d.w) != 0);   // wave-uniform
-    if (flagged != 0 && (threadIdx.x & 63u) == 0) a.bitmap[item >> 6] = flagged;
+    const uint64_t flagged = __ballot(f.live && (d.x | d.y | d.z | d.w) != 0);   // wave-uniform
+    if (flagged != 0 && (threadIdx.x & 63u) == 0) a.bitmap[f.item >> 6] = flagged;
 }
 
 // One lane reads one bitmap word; a workgroup whose 256 words are zero ends there. The waves then

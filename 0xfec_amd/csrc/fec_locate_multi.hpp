@@ -18,6 +18,7 @@
 
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
+#include "fec_verify.hpp"
 #include "gf256.h"
 
 namespace fk {
@@ -181,18 +182,10 @@ GF_HD inline int32_t locate_multi_count(const uint32_t* bad, uint32_t words, boo
     return unknown || count > T ? kLocateUnknown : (int32_t)count;
 }
 
-// Launch 1, the scan (verify's flat launch: item = one 16-byte column chunk of one block, all m <= 16
-// rows in one pass): wave w of the launch writes the ballot of its lanes that hold a nonzero
-// syndrome into bitmap[w], and only if the ballot is nonzero. The bitmap is zero on entry.
-struct LocateMultiScanArgs {
-    const uint8_t* in;      // data shard 0 of block 0
-    const uint8_t* par;     // parity shard 0 of block 0
-    uint64_t in_bs, par_bs, ss;
-    uint32_t k, m;
-    uint32_t len, cps;
-    uint32_t total;         // nblocks * cps (<= 2^31 per launch)
-    FastDiv div_cps;
-    const uint32_t* tabs;   // the code's m * k PermTabs
+// Launch 1, the scan (verify's flat launch, fec_verify.hpp SyndromeArgs, all m <= 16 rows of the code
+// in one pass): wave w of the launch writes the ballot of its lanes that hold a nonzero syndrome into
+// bitmap[w], and only if the ballot is nonzero. The bitmap is zero on entry.
+struct LocateMultiScanArgs : SyndromeArgs {
     uint64_t* bitmap;       // one word per wave of the launch: 4 * grid
 };
 

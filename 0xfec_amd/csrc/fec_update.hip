@@ -3,7 +3,7 @@
 // old_j ^ new_j (update) or data_j (encode-idx). The verify kernel's body (fec_verify.hip): the
 // accumulators start from the stored parity; here only the masked columns are folded in, and the
 // accumulators are stored back.
-#include "fec_device.hpp"
+#include "fec_flat.hpp"
 #include "fec_update.hpp"
 
 namespace fk {
@@ -38,13 +38,8 @@ __global__ __launch_bounds__(kThreads) void rs_update_kernel(UpdateArgs a) {
     const gf::PermTab* tabs = stage_tabs<LDS_TABS>(a.tabs, a.m * a.k * 8, smem);
     if constexpr (LDS_TABS) __syncthreads();
     const uint32_t k = a.k, m = a.m, kw = (k + 31u) >> 5;
-    // the grid is exactly the items' workgroups; a lane past the end repeats the last item and
-    // stores nothing, so every lane of a wave reaches the ballots below
-    const uint32_t item = xcd_order() * kThreads + threadIdx.x;
-    const bool live = item < a.total;
-    const uint32_t it = min(item, a.total - 1u);
-    const uint32_t b = fdiv(it, a.div_cps);
-    const uint32_t c = it - b * a.cps;
+    const FlatItem f = flat_item(a.total, a.cps, a.div_cps);
+    const uint32_t b = f.b, c = f.c;
     const bool scalar = a.cps >= 32u;   // uniform
     const uint32_t bfirst = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
     auto word = [&](uint32_t w) -> uint32_t {   // the lane's block's columns 32 w .. 32 w + 31 below k
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void rs_update_kernel(UpdateArgs a) {
             }
         }
     }
-    if (live && go) {
+    if (f.live && go) {
 #pragma unroll
         for (int r = 0; r < MAXM; ++r)
             if (r < (int)m) store_chunk<true>(par + (uint64_t)r * a.ss, as_uint4(acc[r]), a.len - c * kChunk);

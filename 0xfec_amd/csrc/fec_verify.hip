@@ -2,7 +2,7 @@
 // block holds equal what the encode would write from its data? The generic encode's body
 // (fec_encode.hip rs_encode_kernel) with the stored parity folded in and nothing written but one
 // word per bad block.
-#include "fec_device.hpp"
+#include "fec_flat.hpp"
 #include "fec_verify.hpp"
 
 namespace fk {
@@ -23,13 +23,8 @@ __global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs a) {
     const gf::PermTab* tabs = stage_tabs<LDS_TABS>(a.tabs, a.m * a.k * 8, smem);
     if constexpr (LDS_TABS) __syncthreads();
     const uint32_t k = a.k, m = a.m;
-    // the grid is exactly the items' workgroups; a lane past the end repeats the last item and
-    // reports nothing, so every lane of a wave reaches the ballots below
-    const uint32_t item = xcd_order() * kThreads + threadIdx.x;
-    const bool live = item < a.total;
-    const uint32_t it = min(item, a.total - 1u);
-    const uint32_t b = fdiv(it, a.div_cps);
-    const uint32_t c = it - b * a.cps;
+    const FlatItem f = flat_item(a.total, a.cps, a.div_cps);
+    const uint32_t b = f.b, c = f.c;
     const uint8_t* src = a.in + (uint64_t)b * a.in_bs + (uint64_t)c * kChunk;
     const uint8_t* par = a.par + (uint64_t)b * a.par_bs + (uint64_t)c * kChunk;
     uint32_t acc[MAXM][4];
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs a) {
     for (int r = 0; r < MAXM; ++r)
         if (r < (int)m) d.x |= acc[r][0], d.y |= acc[r][1], d.z |= acc[r][2], d.w |= acc[r][3];
     d = keep_bytes(d, a.len - c * kChunk);
-    const bool bad = live && (d.x | d.y | d.z | d.w) != 0;
+    const bool bad = f.live && (d.x | d.y | d.z | d.w) != 0;
     uint64_t todo = __ballot(bad);   // wave-uniform
     const uint32_t lane = threadIdx.x & 63u;
     while (todo) {

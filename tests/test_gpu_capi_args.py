@@ -5,12 +5,12 @@ each region in order: base and strides 16-byte aligned, then shard_stride >= sha
 17-byte shards at stride 32. Every case returns before any launch."""
 import pytest
 
+from arena import CANARY
 from capi_calls import CALLS, layout
 
 pytestmark = pytest.mark.gpu
 
 OK, INV, ALIGN = 0, -1, -7   # FEC_OK, FEC_ERR_INVALID_ARG, FEC_ERR_ALIGNMENT
-CANARY = 0xC7
 
 
 def expected(call, v):

@@ -11,17 +11,12 @@ import itertools
 import numpy as np
 import pytest
 
+from arena import torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1), (2, 1), (3, 2), (6, 2), (8, 4), (16, 8), (20, 10), (5, 11), (31, 1), (10, 22)]
 LENS = [1, 2, 3, 15, 16, 17, 33, 1202, 1436]
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
 
 
 @pytest.fixture(scope="module")

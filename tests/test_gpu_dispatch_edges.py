@@ -19,28 +19,12 @@ Every array the library may write is compared whole: a rebuilt or encoded shard 
 import numpy as np
 import pytest
 
+from arena import codec, rup16, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 FILL_ERASED = 0x3C
 FILL_OUT = 0xEE
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
 
 
 def make_batch(oracle, rng, k, m, L, B):

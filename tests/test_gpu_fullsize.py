@@ -16,17 +16,12 @@ ReconstructData, :124). Checked:
 import numpy as np
 import pytest
 
+from arena import torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 PAYLOAD, L, S = 1200, 1202, 1216
 SEED = 0x0FEC
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
 
 
 def _batch(torch, codec, k, m, B):

@@ -91,13 +91,12 @@ import ctypes
 import numpy as np
 import pytest
 
+from arena import CANARY, GUARD, MUL, check_arena, torch  # noqa: F401
 from test_gpu_wide import erase_block, pick, ref_reconstruct
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC7
 ERASED = 0x5A
-GUARD = 256
 GAP = 80            # canary bytes between two regions of one arena
 B = 61
 WORD_GUARD = 64     # canary words on either side of a mask or status array
@@ -109,26 +108,10 @@ RS_LENGTHS = {(8, 4): [1202, 33, 16, 7], (2, 1): [1202, 33], (5, 3): [1202, 33],
 
 
 @pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
 def codec(fec):
     c = fec.Codec(0)
     yield c
     c.close()
-
-
-@pytest.fixture(scope="module")
-def MUL(oracle):
-    t = np.zeros((256, 256), dtype=np.uint8)
-    for a in range(256):
-        for b in range(a, 256):
-            t[a, b] = t[b, a] = oracle.gf_mul(a, b)
-    return t
 
 
 # ------------------------------------------------------------------ arenas, regions, layouts
@@ -232,13 +215,6 @@ def guarded_words(values):
     view = whole[WORD_GUARD:WORD_GUARD + values.size]
     view[:] = values.ravel()
     return whole, view
-
-
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
 
 
 def phases(kind, salt):

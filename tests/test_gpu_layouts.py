@@ -13,11 +13,11 @@ kernel that lets the bytes of a partial tail chunk past L leak into its output f
 import numpy as np
 import pytest
 
+from arena import CANARY, GUARD, Region, canary_image, check_arena, codec, place, rup16, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC7
 ERASED = 0x5A
-GUARD = 256
 B = 67          # waves straddle blocks, the last workgroup is ragged
 
 LAYOUTS = ["interleaved_slack", "split_parity_first", "shard_major", "shard_major_split"]
@@ -28,86 +28,16 @@ RS_CASES = [(2, 1, 1202), (6, 2, 1202), (8, 4, 1202), (16, 8, 1202), (20, 10, 12
 STEPS = ["encode", "reconstruct", "recover_m", "recover_1"]
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
-
-
-class Region:
-    """Shard slots at off + b*bs + r*ss (byte offsets into an arena)."""
-
-    def __init__(self, off, bs, ss, rows):
-        self.off, self.bs, self.ss, self.rows = off, bs, ss, rows
-        assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-
-    def at(self, b, r):
-        return self.off + b * self.bs + r * self.ss
-
-    def index(self, lo, hi):
-        """[B, rows, hi - lo] arena indices of bytes [lo, hi) of every slot."""
-        return (self.off + np.arange(B)[:, None, None] * self.bs + np.arange(self.rows)[None, :, None] * self.ss +
-                np.arange(lo, hi)[None, None, :])
-
-    def end(self):
-        """One past the last byte of the last slot, each slot taken as ss bytes (the header asks
-        for every slot to be readable over its whole shard stride)."""
-        return self.off + (B - 1) * self.bs + (self.rows - 1) * self.ss + self.ss
-
-
-class Arena:
-    def __init__(self, regions):
-        self.size = max(r.end() for r in regions) + GUARD
-        assert min(r.off for r in regions) >= GUARD
-        self.img = np.full(self.size, CANARY, dtype=np.uint8)
-
-
 def make_layout(name, k, m, L, slots):
     """(arena, data region, parity region, out arena, out region) for one layout; every offset and
-    stride a multiple of 16, at least GUARD canary bytes before the first and after the last slot."""
-    R = rup16(L)
-    n = k + m
-    if name == "interleaved_slack":
-        ss = R + 32
-        bs = n * ss + 48
-        data = Region(GUARD, bs, ss, k)
-        par = Region(GUARD + k * ss, bs, ss, m)
-    elif name == "split_parity_first":
-        ss = R + 16
-        par = Region(GUARD, m * ss + 16, ss, m)
-        data = Region(par.end() + 80, k * ss + 48, ss, k)
-    elif name == "shard_major":
-        sp = R + 16
-        ss = B * sp
-        data = Region(GUARD, sp, ss, k)
-        par = Region(GUARD + k * ss, sp, ss, m)
-    elif name == "shard_major_split":
-        sp = R + 16
-        ss = B * sp
-        par = Region(GUARD, sp, ss, m)
-        gap = 208
-        assert gap % ss != 0
-        data = Region(GUARD + m * ss + gap, sp, ss, k)
-    else:
-        raise ValueError(name)
+    stride a multiple of 16, at least GUARD canary bytes before the first and after the last slot.
+    The out region of a recover lies in an arena of its own, shard-major where the inputs are."""
+    data, par = place(name, k, m, L, B)
     if name.startswith("shard_major"):
-        out = Region(GUARD, sp, ss, slots)
+        out = Region(GUARD, data.bs, data.ss, slots, B)
     else:
-        out = Region(GUARD, slots * ss + 32, ss, slots)
-    assert data.ss == par.ss == out.ss
-    return Arena([data, par]), data, par, Arena([out]), out
+        out = Region(GUARD, slots * data.ss + 32, data.ss, slots, B)
+    return canary_image([data, par]), data, par, canary_image([out]), out
 
 
 def make_masks(rng, k, m):
@@ -180,18 +110,11 @@ def rs_case(oracle, k, m, L):
 def fill_damaged(arena, data, par, c, k, L):
     """The encoded batch with its erased shards overwritten (bytes [0, round_up(L, 16)))."""
     R = rup16(L)
-    arena.img[data.index(0, L)] = c["dmg"][:, :k]
-    arena.img[par.index(0, L)] = c["dmg"][:, k:]
+    arena[data.index(0, L)] = c["dmg"][:, :k]
+    arena[par.index(0, L)] = c["dmg"][:, k:]
     for reg, lost in ((data, c["lost"][:, :k]), (par, c["lost"][:, k:])):
         pad = reg.index(L, R)
-        arena.img[pad[lost]] = ERASED
-
-
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
+        arena[pad[lost]] = ERASED
 
 
 def expect_sync(codec, fec, st_want):
@@ -210,11 +133,11 @@ def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
     masks = c["masks"] if masks is None else masks
     h = codec.handle
     if step == "encode":
-        arena.img[data.index(0, L)] = c["sh"][:, :k]
-        model = arena.img.copy()
+        arena[data.index(0, L)] = c["sh"][:, :k]
+        model = arena.copy()
         model[par.index(0, L)] = c["sh"][:, k:]
         model[par.index(L, R)] = 0
-        dev = torch.from_numpy(arena.img).cuda()
+        dev = torch.from_numpy(arena).cuda()
         p = dev.data_ptr()
         assert p % 16 == 0
         rc = fec.lib.fec_rs_encode_batch(h, k, m, L, B, p + data.off, data.bs, p + par.off, par.bs, data.ss,
@@ -224,12 +147,12 @@ def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
         check_arena(dev.cpu().numpy(), model, "encode")
         return
     fill_damaged(arena, data, par, c, k, L)
-    dev = torch.from_numpy(arena.img).cuda()
+    dev = torch.from_numpy(arena).cuda()
     p = dev.data_ptr()
     assert p % 16 == 0
     dm = torch.from_numpy(masks.view(np.int32).copy()).cuda()
     st = torch.full((B,), 99, dtype=torch.int32, device="cuda")
-    model = arena.img.copy()
+    model = arena.copy()
     lost_d, e_d, few = c["lost"][:, :k], c["e_d"], c["few"]
     if step == "reconstruct":
         rebuilt = lost_d & ~few[:, None]                       # erased data shards of recoverable blocks
@@ -243,7 +166,7 @@ def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
         assert np.array_equal(st.cpu().numpy(), st_want)
         check_arena(dev.cpu().numpy(), model, "in-place reconstruct")
         return
-    omodel = oarena.img.copy()
+    omodel = oarena.copy()
     st_want = np.where(e_d == 0, 0, np.where(few, fec.FEC_ERR_TOO_FEW_SHARDS,
                                              np.where(e_d > slots, fec.FEC_ERR_INVALID_ARG, e_d)))
     assert (st_want > 0).any()
@@ -252,7 +175,7 @@ def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
             o = out.at(b, r)
             omodel[o:o + L] = c["rec"][b, i]
             omodel[o + L:o + R] = 0
-    odev = torch.from_numpy(oarena.img).cuda()
+    odev = torch.from_numpy(oarena).cuda()
     op = odev.data_ptr()
     assert op % 16 == 0
     rc = fec.lib.fec_rs_recover_batch(h, k, m, L, B, p + data.off, data.bs, p + par.off, par.bs, data.ss,
@@ -284,11 +207,11 @@ def test_xor_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec
     oracle.xor_encode(k, sh)
     h = codec.handle
     arena, data, par, _, _ = make_layout(layout, k, 1, L, 1)
-    arena.img[data.index(0, L)] = sh[:, :k]
-    model = arena.img.copy()
+    arena[data.index(0, L)] = sh[:, :k]
+    model = arena.copy()
     model[par.index(0, L)] = sh[:, k:]
     model[par.index(L, R)] = 0
-    dev = torch.from_numpy(arena.img).cuda()
+    dev = torch.from_numpy(arena).cuda()
     p = dev.data_ptr()
     assert fec.lib.fec_xor_encode_batch(h, k, L, B, p + data.off, data.bs, p + par.off, par.bs, data.ss,
                                         fec.FEC_DEVICE) == fec.FEC_OK
@@ -313,12 +236,12 @@ def test_xor_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec
     assert np.array_equal(st_ref != 0, fail) and fail.any() and (kind == 2).any()
     arena, data, par, _, _ = make_layout(layout, k, 1, L, 1)
     fill_damaged(arena, data, par, dict(dmg=dmg, lost=lost), k, L)
-    model = arena.img.copy()
+    model = arena.copy()
     rebuilt = lost[:, :k] & (kind == 2)[:, None]
     assert np.array_equal(rec[:, :k][rebuilt], sh[:, :k][rebuilt])
     model[data.index(0, L)[rebuilt]] = rec[:, :k][rebuilt]
     model[data.index(L, R)[rebuilt]] = 0
-    dev = torch.from_numpy(arena.img).cuda()
+    dev = torch.from_numpy(arena).cuda()
     p = dev.data_ptr()
     dm = torch.from_numpy(masks.view(np.int32).copy()).cuda()
     st = torch.full((B,), 99, dtype=torch.int32, device="cuda")

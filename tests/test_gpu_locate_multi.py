@@ -22,11 +22,10 @@ import itertools
 import numpy as np
 import pytest
 
+from arena import CANARY, STALE, check_arena, codec, encoded_arena, gf, shards, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC7
-GUARD = 256
-STALE = 0x7EADBEEF
 UNKNOWN = -2
 MAX_BAD = 8
 
@@ -37,78 +36,6 @@ CODES = [(1, 2), (2, 2), (6, 3), (8, 4), (20, 10), (4, 16), (240, 16), (31, 1), 
 LAYOUTS = ["interleaved", "split"]
 NPATTERNS = 14
 BRUTE_N = 12
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def gf(oracle):
-    """The oracle's field: MUL[a, b] = gf_mul(a, b), INV[a] (INV[0] = 0)."""
-    mul = np.array([[oracle.gf_mul(a, b) for b in range(256)] for a in range(256)], dtype=np.uint8)
-    inv = np.zeros(256, dtype=np.uint8)
-    a, b = np.nonzero(mul == 1)
-    inv[a] = b
-    return mul, inv
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
-
-
-class Region:
-    """Shard slots at off + b*bs + r*ss (byte offsets into an arena) of B blocks."""
-
-    def __init__(self, off, bs, ss, rows, B):
-        self.off, self.bs, self.ss, self.rows, self.B = off, bs, ss, rows, B
-        assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-
-    def at(self, b, r):
-        return self.off + b * self.bs + r * self.ss
-
-    def index(self, lo, hi):
-        return (self.off + np.arange(self.B)[:, None, None] * self.bs +
-                np.arange(self.rows)[None, :, None] * self.ss + np.arange(lo, hi)[None, None, :])
-
-    def end(self):
-        return self.off + (self.B - 1) * self.bs + max(self.rows - 1, 0) * self.ss + self.ss
-
-
-def make_layout(name, k, m, L, B):
-    """(arena image, data region, parity region): slots with slack, block strides with gaps."""
-    R = rup16(L)
-    n = k + m
-    if name == "interleaved":
-        ss = R + 32
-        bs = n * ss + 48
-        data = Region(GUARD, bs, ss, k, B)
-        par = Region(GUARD + k * ss, bs, ss, m, B)
-    elif name == "split":   # parity below the data in memory
-        ss = R + 16
-        par = Region(GUARD, m * ss + 16, ss, m, B)
-        data = Region(par.end() + 80, k * ss + 48, ss, k, B)
-    else:
-        raise ValueError(name)
-    img = np.full(max(data.end(), par.end()) + GUARD, CANARY, dtype=np.uint8)
-    return img, data, par
-
-
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
 
 
 _NULL = {}
@@ -178,11 +105,8 @@ class Batch:
         self.brute = self.n <= BRUTE_N
         # larger codes: at most m - T corrupt shards per block (m = 0: nothing can be inconsistent)
         self.cap = self.n if self.brute or m == 0 else m - T
-        img, self.data, self.par = make_layout(layout, k, m, L, B)
         self.rng = rng = np.random.default_rng(seed)
-        img[self.data.index(0, L)] = rng.integers(0, 256, (B, k, L), dtype=np.uint8)
-        if m:
-            img = self.encode(img)
+        img, self.data, self.par = encoded_arena(codec, fec, torch, layout, k, m, L, B, rng)
         self.clean = img.copy()
         self.clean.setflags(write=False)
         self.hit = [set() for _ in range(B)]      # the shards of each block with a changed byte in [0, L)
@@ -209,28 +133,9 @@ class Batch:
             elif t[b] <= m - T:
                 assert self.want[b] == UNKNOWN, (b, pats[b])
 
-    def encode(self, img):
-        """The arena with its parity made by fec_rs_encode_batch, the zero pad put back to canary."""
-        fec, k, m, L = self.fec, self.k, self.m, self.L
-        dev = self.torch.from_numpy(img).cuda()
-        p = dev.data_ptr()
-        assert fec.lib.fec_rs_encode_batch(self.codec.handle, k, m, L, self.B, p + self.data.off, self.data.bs,
-                                           p + self.par.off, self.par.bs, self.data.ss, fec.FEC_DEVICE) == fec.FEC_OK
-        assert self.codec.lib_sync_rc() == fec.FEC_OK
-        img = dev.cpu().numpy()
-        pad = self.par.index(L, rup16(L))
-        assert (img[pad] == 0).all()
-        img[pad] = CANARY          # the parity slots too hold canary from L on
-        return img
-
     def shards(self, img):
         """[B, n, S] copy of the arena's slots."""
-        S = self.data.ss
-        out = np.empty((self.B, self.n, S), dtype=np.uint8)
-        out[:, :self.k] = img[self.data.index(0, S)]
-        if self.m:
-            out[:, self.k:] = img[self.par.index(0, S)]
-        return out
+        return shards(img, self.data, self.par)
 
     def flip(self, b, s, x, v=None):
         """shard s of block b, byte x ^= v (nonzero). Nothing for a byte already changed, and nothing

@@ -8,16 +8,11 @@ a twin that skipped or re-read shards would show up here before it skewed a benc
 import numpy as np
 import pytest
 
+from arena import torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 S, L = 1216, 1202
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
 
 
 @pytest.mark.parametrize("k,m", [(2, 1), (8, 4), (16, 8), (20, 10)])

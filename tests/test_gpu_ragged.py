@@ -12,13 +12,12 @@ kind of block.
 """
 import numpy as np
 import pytest
-from numpy.lib.stride_tricks import as_strided
+
+from arena import CANARY, GUARD, Region, canary_image, check_arena, codec, rup16, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC7
 ERASED = 0x5A
-GUARD = 256
 GAP = 208
 S = 1216
 MAXL = 1202
@@ -36,10 +35,6 @@ DEC_SHAPES = [(8, 4), (20, 10), (2, 1), (10, 22), (16, 16)]
 KIND_COMPLETE, KIND_ONE, KIND_MAX, KIND_FEW, KIND_FIRSTK = range(5)
 
 
-def rup16(x):
-    return (x + 15) // 16 * 16
-
-
 def default_lens(nb):
     lens = np.array([PATTERN[b % 14] for b in range(nb)], dtype=np.uint32)
     if nb >= 216:
@@ -54,42 +49,19 @@ def span_mask(lo, hi, width):
     return (x >= np.asarray(lo)[:, None, None]) & (x < np.asarray(hi)[:, None, None])
 
 
-class Region:
-    """nb x rows shard slots of `ss` bytes at off + b*bs + r*ss of an arena image."""
-
-    def __init__(self, off, nb, rows, bs, ss=S):
-        assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-        self.off, self.nb, self.rows, self.bs, self.ss = off, nb, rows, bs, ss
-
-    def end(self):
-        return self.off + (self.nb - 1) * self.bs + self.rows * self.ss
-
-    def view(self, img):
-        """Writable [nb, rows, ss] view of the slots in the image."""
-        return as_strided(img[self.off:], shape=(self.nb, self.rows, self.ss), strides=(self.bs, self.ss, 1))
-
-
 def make_arena(layout, nb, k, m, slots, ss=S):
     """(image, data, parity, out): one canary-filled arena holding the three regions."""
     n = k + m
     if layout == "interleaved":
-        data = Region(GUARD, nb, k, n * ss, ss)
-        par = Region(GUARD + k * ss, nb, m, n * ss, ss)
+        data = Region(GUARD, n * ss, ss, k, nb)
+        par = Region(GUARD + k * ss, n * ss, ss, m, nb)
         top = GUARD + nb * n * ss
     else:   # split: the parity region below the data region
-        par = Region(GUARD, nb, m, m * ss, ss)
-        data = Region(par.end() + GAP, nb, k, k * ss, ss)
+        par = Region(GUARD, m * ss, ss, m, nb)
+        data = Region(par.end() + GAP, k * ss, ss, k, nb)
         top = data.end()
-    out = Region(top + GAP, nb, max(slots, 1), max(slots, 1) * ss, ss)
-    img = np.full(out.end() + GUARD, CANARY, dtype=np.uint8)
-    return img, data, par, out
-
-
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
+    out = Region(top + GAP, max(slots, 1) * ss, ss, max(slots, 1), nb)
+    return canary_image([data, par, out]), data, par, out
 
 
 def make_masks(rng, k, m, nb):
@@ -200,20 +172,6 @@ def dec_case(oracle, k, m, nb=B, lens=None, key=None, all_ok=False):
     return _dec_cases[ck]
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
 def upload(torch, img):
     dev = torch.from_numpy(img).cuda()
     assert dev.data_ptr() % 16 == 0
@@ -228,7 +186,7 @@ def shards_of(dev, reg, rows=None):
     """The [nb, rows, S] tensor view of a compact region of the device arena."""
     rows = reg.rows if rows is None else rows
     assert reg.bs == rows * reg.ss
-    return dev[reg.off:reg.off + reg.nb * reg.bs].view(reg.nb, rows, reg.ss)
+    return dev[reg.off:reg.off + reg.B * reg.bs].view(reg.B, rows, reg.ss)
 
 
 def expect_sync(codec, fec, st_want):
@@ -270,7 +228,7 @@ def run_encode(codec, fec, torch, c, k, m, layout, oversize_status=False):
     dl = dev_words(torch, c["lens"])
     st = torch.full((nb,), 99, dtype=torch.int32, device="cuda")
     if layout == "interleaved":
-        codec.rs_encode_ragged(k, m, shards_of(dev, Region(data.off, nb, k + m, data.bs), k + m), dl, status=st,
+        codec.rs_encode_ragged(k, m, shards_of(dev, Region(data.off, data.bs, S, k + m, nb), k + m), dl, status=st,
                                max_shard_len=MAXL)
     else:
         codec.rs_encode_ragged_split(k, m, shards_of(dev, data), shards_of(dev, par), dl, status=st,
@@ -318,7 +276,7 @@ def run_decode(codec, fec, torch, c, k, m, layout, slots):
     st = torch.full((nb,), 99, dtype=torch.int32, device="cuda")
     p = dev.data_ptr()
     if slots == 0 and layout == "interleaved":
-        codec.rs_reconstruct_ragged(k, m, shards_of(dev, Region(data.off, nb, k + m, data.bs), k + m), dm, dl,
+        codec.rs_reconstruct_ragged(k, m, shards_of(dev, Region(data.off, data.bs, S, k + m, nb), k + m), dm, dl,
                                     status=st, max_shard_len=MAXL)
     elif slots == 0:
         codec.rs_reconstruct_ragged_split(k, m, shards_of(dev, data), shards_of(dev, par), dm, dl, status=st,

@@ -12,16 +12,11 @@ import sys
 import numpy as np
 import pytest
 
+from arena import torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
 
 
 @pytest.fixture(scope="module")

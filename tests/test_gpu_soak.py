@@ -17,24 +17,12 @@ XOR(k, 1) cases run beside them. The draws are fixed by the seed, so a failure n
 import numpy as np
 import pytest
 
+from arena import codec, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 CASES = 400
 LENS = [1, 15, 16, 17, 200, 495, 496, 497, 512, 513, 1008, 1017, 1024, 1025, 1202, 1436]
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
 
 
 def _draw(rng):

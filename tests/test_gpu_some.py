@@ -11,11 +11,11 @@ the result; of those the model takes only the shards the call was asked to rebui
 import numpy as np
 import pytest
 
+from arena import CANARY, canary_image, check_arena, codec, place, rup16, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC7
 ERASED = 0x5A
-GUARD = 256
 B = 67          # waves straddle blocks, the last workgroup is ragged
 TOO_FEW = -4
 
@@ -25,67 +25,8 @@ CODES = [(2, 1), (3, 2), (8, 4), (16, 8), (20, 10), (10, 22), (1, 31), (31, 1), 
 LAYOUTS = ["interleaved_slack", "split_parity_first", "shard_major"]
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
-
-
 def low_mask(n):
     return (1 << n) - 1
-
-
-class Region:
-    """Shard slots at off + b*bs + r*ss (byte offsets into an arena)."""
-
-    def __init__(self, off, bs, ss, rows):
-        self.off, self.bs, self.ss, self.rows = off, bs, ss, rows
-        assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-
-    def index(self, lo, hi):
-        """[B, rows, hi - lo] arena indices of bytes [lo, hi) of every slot."""
-        return (self.off + np.arange(B)[:, None, None] * self.bs + np.arange(self.rows)[None, :, None] * self.ss +
-                np.arange(lo, hi)[None, None, :])
-
-    def end(self):
-        return self.off + (B - 1) * self.bs + max(self.rows - 1, 0) * self.ss + self.ss
-
-
-def make_layout(name, k, m, L):
-    """(arena image, data region, parity region); every offset and stride a multiple of 16, at least
-    GUARD canary bytes before the first and after the last slot."""
-    R = rup16(L)
-    n = k + m
-    if name == "interleaved_slack":
-        ss = R + 32
-        bs = n * ss + 48
-        data = Region(GUARD, bs, ss, k)
-        par = Region(GUARD + k * ss, bs, ss, m)
-    elif name == "split_parity_first":
-        ss = R + 16
-        par = Region(GUARD, m * ss + 16, ss, m)
-        data = Region(par.end() + 80, k * ss + 48, ss, k)
-    elif name == "shard_major":
-        sp = R + 16
-        ss = B * sp
-        data = Region(GUARD, sp, ss, k)
-        par = Region(GUARD + k * ss, sp, ss, m)
-    else:
-        raise ValueError(name)
-    img = np.full(max(data.end(), par.end()) + GUARD, CANARY, dtype=np.uint8)
-    return img, data, par
 
 
 def make_masks(rng, k, m):
@@ -179,19 +120,13 @@ def fill_damaged(img, data, par, c, k, L):
         img[reg.index(L, R)[lost]] = ERASED
 
 
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
-
-
 def run_some(codec, fec, torch, c, layout, k, m, L, want=None, dev_masks=None, dev_want=None, mutate=None):
     """One call on one layout; checks the whole arena, the statuses and the sticky code against the
     model. want: uint32 [B] or None (every shard); dev_masks / dev_want: what the device is given
     instead (stray bits). Returns (arena before the call, arena after, statuses, rebuilt [B, n])."""
     n, R = k + m, rup16(L)
-    img, data, par = make_layout(layout, k, m, L)
+    data, par = place(layout, k, m, L, B)
+    img = canary_image([data, par])
     fill_damaged(img, data, par, c, k, L)
     if mutate:
         mutate(img, data, par)

@@ -17,10 +17,9 @@ loads); shards of 497 bytes and more put at most 3 blocks into a wave (masks by 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from arena import CANARY, Region, canary_image, check_arena, codec, place, rup16, torch  # noqa: F401
 
-CANARY = 0xC7
-GUARD = 256
+pytestmark = pytest.mark.gpu
 
 LENS = [1, 15, 16, 17, 33, 1202]
 # (33,20): two parity row passes and two mask words; (32,0): nothing to write
@@ -28,67 +27,16 @@ CODES = [(2, 1), (8, 4), (20, 10), (31, 1), (33, 20), (32, 0)]
 LAYOUTS = ["interleaved", "split"]
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
-
-
-class Region:
-    """Shard slots at off + b*bs + r*ss (byte offsets into an arena) of B blocks."""
-
-    def __init__(self, off, bs, ss, rows, B):
-        self.off, self.bs, self.ss, self.rows, self.B = off, bs, ss, rows, B
-        assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-
-    def end(self):
-        return self.off + (self.B - 1) * self.bs + max(self.rows - 1, 0) * self.ss + self.ss
-
-    def view(self, img, lo, hi):
-        """Bytes [lo, hi) of every slot as a [B, rows, hi - lo] view of the arena (slots do not overlap)."""
-        assert self.end() <= img.size and hi <= self.ss
-        v = np.lib.stride_tricks.as_strided(img[self.off:], (self.B, self.rows, self.ss), (self.bs, self.ss, 1),
-                                            writeable=img.flags.writeable)
-        return v[:, :, lo:hi]
-
-
 def make_layout(name, k, m, L, B):
-    """(arena image, old data region, new data region, parity region)."""
-    R = rup16(L)
-    if name == "interleaved":   # old data and parity in one [B][k+m] region, new data apart
-        ss = R + 32
-        bs = (k + m) * ss + 48
-        old = Region(GUARD, bs, ss, k, B)
-        par = Region(GUARD + k * ss, bs, ss, m, B)
+    """(arena image, old data region, new data region, parity region): the old data and the parity as
+    the layout places data and parity, the new data apart, above both."""
+    old, par = place(name, k, m, L, B)
+    ss = old.ss
+    if name == "interleaved":   # old data and parity in one [B][k+m] region
         new = Region(max(old.end(), par.end()) + 96, k * ss + 16, ss, k, B)
-    elif name == "split":       # three regions, parity lowest
-        ss = R + 16
-        par = Region(GUARD, m * ss + 16, ss, m, B)
-        old = Region(par.end() + 80, k * ss + 48, ss, k, B)
+    else:                       # three regions, parity lowest
         new = Region(old.end() + 32, k * ss + 32, ss, k, B)
-    else:
-        raise ValueError(name)
-    img = np.full(new.end() + GUARD, CANARY, dtype=np.uint8)
-    return img, old, new, par
-
-
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
+    return canary_image([old, new, par]), old, new, par
 
 
 def pack_masks(fec, cols, W, stray=False):

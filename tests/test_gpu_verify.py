@@ -15,79 +15,16 @@ import re
 import numpy as np
 import pytest
 
+from arena import CANARY, GUARD, STALE, check_arena, codec, encoded_arena, rup16, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CANARY = 0xC7
-GUARD = 256
-STALE = 0x7EADBEEF
 
 LENS = [1, 15, 16, 17, 33, 1202]
 # (33,20): two parity row passes, (1,40): three; (32,0): nothing to compare
 CODES = [(2, 1), (8, 4), (16, 8), (20, 10), (31, 1), (32, 0), (33, 20), (1, 40)]
 LAYOUTS = ["interleaved", "split"]
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
-
-
-class Region:
-    """Shard slots at off + b*bs + r*ss (byte offsets into an arena) of B blocks."""
-
-    def __init__(self, off, bs, ss, rows, B):
-        self.off, self.bs, self.ss, self.rows, self.B = off, bs, ss, rows, B
-        assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-
-    def at(self, b, r):
-        return self.off + b * self.bs + r * self.ss
-
-    def index(self, lo, hi):
-        return (self.off + np.arange(self.B)[:, None, None] * self.bs +
-                np.arange(self.rows)[None, :, None] * self.ss + np.arange(lo, hi)[None, None, :])
-
-    def end(self):
-        return self.off + (self.B - 1) * self.bs + max(self.rows - 1, 0) * self.ss + self.ss
-
-
-def make_layout(name, k, m, L, B):
-    """(arena image, data region, parity region): slots with slack, block strides with gaps."""
-    R = rup16(L)
-    n = k + m
-    if name == "interleaved":
-        ss = R + 32
-        bs = n * ss + 48
-        data = Region(GUARD, bs, ss, k, B)
-        par = Region(GUARD + k * ss, bs, ss, m, B)
-    elif name == "split":   # parity below the data in memory
-        ss = R + 16
-        par = Region(GUARD, m * ss + 16, ss, m, B)
-        data = Region(par.end() + 80, k * ss + 48, ss, k, B)
-    else:
-        raise ValueError(name)
-    img = np.full(max(data.end(), par.end()) + GUARD, CANARY, dtype=np.uint8)
-    return img, data, par
-
-
-def check_arena(got, model, what):
-    if not np.array_equal(got, model):
-        bad = np.flatnonzero(got != model)
-        raise AssertionError("%s: %d bytes differ from the model, first at arena offset %d (got 0x%02x, want 0x%02x)"
-                             % (what, bad.size, bad[0], got[bad[0]], model[bad[0]]))
 
 
 class Batch:
@@ -96,20 +33,7 @@ class Batch:
     def __init__(self, codec, fec, torch, layout, k, m, L, B, seed):
         self.codec, self.fec, self.torch = codec, fec, torch
         self.k, self.m, self.L, self.B = k, m, L, B
-        img, self.data, self.par = make_layout(layout, k, m, L, B)
-        rng = np.random.default_rng(seed)
-        img[self.data.index(0, L)] = rng.integers(0, 256, (B, k, L), dtype=np.uint8)
-        if m:
-            dev = torch.from_numpy(img).cuda()
-            p = dev.data_ptr()
-            assert fec.lib.fec_rs_encode_batch(codec.handle, k, m, L, B, p + self.data.off, self.data.bs,
-                                               p + self.par.off, self.par.bs, self.data.ss,
-                                               fec.FEC_DEVICE) == fec.FEC_OK
-            assert codec.lib_sync_rc() == fec.FEC_OK
-            img = dev.cpu().numpy()
-            pad = self.par.index(L, rup16(L))
-            assert (img[pad] == 0).all()
-            img[pad] = CANARY          # the parity slots too hold canary from L on
+        img, self.data, self.par = encoded_arena(codec, fec, torch, layout, k, m, L, B, np.random.default_rng(seed))
         img.setflags(write=False)
         self.img = img
 

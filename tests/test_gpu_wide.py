@@ -10,37 +10,11 @@ and against the original data.
 import numpy as np
 import pytest
 
+from arena import CANARY, GUARD, MUL, codec, rup16, torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ERASED = 0x5A
-CANARY = 0xC7
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU test needs a HIP device"
-    return t
-
-
-@pytest.fixture(scope="module")
-def codec(fec):
-    c = fec.Codec(0).use_torch_stream()
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def MUL(oracle):
-    t = np.zeros((256, 256), dtype=np.uint8)
-    for a in range(256):
-        for b in range(a, 256):
-            t[a, b] = t[b, a] = oracle.gf_mul(a, b)
-    return t
-
-
-def rup16(x):
-    return (x + 15) // 16 * 16
 
 
 def encoded(oracle, rng, B, k, m, L, S=None):
@@ -305,7 +279,6 @@ def test_wide_recover_statuses_order_and_canaries(fec, codec, oracle, torch, k, 
 # ------------------------------------------------------------------ 5. layouts in a guarded arena
 
 ARENA_B = 67
-GUARD = 256
 
 
 class Slots:
