@@ -79,10 +79,8 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 gf::PermTab t = gf::make_permtab(c.matrix[(size_t)(k + r) * k + j]);
                 memcpy(&tabs[((size_t)r * k + j) * 8], &t, sizeof(t));
             }
-        HIP_TRY(hipMalloc(&c.d_prows, (size_t)m * k));
-        HIP_TRY(hipMalloc(&c.d_tabs, tabs.size() * 4));
-        HIP_TRY(hipMemcpy(c.d_prows, c.matrix.data() + (size_t)k * k, (size_t)m * k, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.d_tabs, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c.d_prows.upload(c.matrix.data() + (size_t)k * k, (size_t)m * k));
+        HIP_TRY(c.d_tabs.upload(tabs.data(), tabs.size() * 4));
         // single-erasure plans: data shard E0 lost, parity R0 the first present one; inputs are
         // the other data shards in order, then parity R0 (the first k present shards):
         // x_E0 = inv(A[R0][E0]) * (p_R0 ^ sum_{j != E0} A[R0][j] x_j)   (reed_solomon.go:124)
@@ -100,8 +98,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                         if (j != e0) dst[pos++] = j < k ? gf::mul(inv, row[j]) : inv;
                 }
             c.single_coef = sc;
-            HIP_TRY(hipMalloc(&c.d_single_coef, sc.size() * 4));
-            HIP_TRY(hipMemcpy(c.d_single_coef, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(c.d_single_coef.upload(sc.data(), sc.size() * 4));
         }
         if (k + m <= FEC_MAX_DECODE_SHARDS && fk::direct_table_words((uint32_t)k, (uint32_t)m) * 4 <= 16 * 1024) {
             // the same plans expanded to PermTabs (k*m*k*32 bytes; small codes only)
@@ -118,15 +115,13 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                         ++pos;
                     }
                 }
-            HIP_TRY(hipMalloc(&c.d_single, st.size() * 4));
-            HIP_TRY(hipMemcpy(c.d_single, st.data(), st.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(c.d_single.upload(st.data(), st.size() * 4));
         }
         {   // the locate call's ratio -> column table and the field's inverses (fec_locate.hpp)
             uint8_t lt[fk::kLocateTabBytes];
             if (!fk::locate_table(lt, c.matrix.data() + (size_t)k * k, (uint32_t)k, (uint32_t)m))
                 return FEC_ERR_INVALID_ARG;
-            HIP_TRY(hipMalloc(&c.d_loctab, sizeof(lt)));
-            HIP_TRY(hipMemcpy(c.d_loctab, lt, sizeof(lt), hipMemcpyHostToDevice));
+            HIP_TRY(c.d_loctab.upload(lt, sizeof(lt)));
         }
         if (fk::locate_needs_carry_tabs((uint32_t)k, (uint32_t)m)) {
             // locate's later passes, each row 0's tables followed by its own rows' (fec_locate.hpp)
@@ -139,8 +134,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 memcpy(&carry[p * slab], tabs.data(), row * 4);
                 memcpy(&carry[p * slab + row], &tabs[r0 * row], rows * row * 4);
             }
-            HIP_TRY(hipMalloc(&c.d_loc_carry, carry.size() * 4));
-            HIP_TRY(hipMemcpy(c.d_loc_carry, carry.data(), carry.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(c.d_loc_carry.upload(carry.data(), carry.size() * 4));
         }
         if (m >= 1 && m <= fk::kLocateMultiRows) {
             // the locate-multi call's coefficients as PermTabs, then the field's tables
@@ -153,8 +147,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 memcpy(&lm[(size_t)i * 8], &t, sizeof(t));
             }
             memcpy(&lm[(size_t)m * m * 8], &gf::kTables, sizeof(gf::Tables));
-            HIP_TRY(hipMalloc(&c.d_lmtab, lm.size() * 4));
-            HIP_TRY(hipMemcpy(c.d_lmtab, lm.data(), lm.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(c.d_lmtab.upload(lm.data(), lm.size() * 4));
         }
         const std::vector<uint8_t> leaves = dyadic_leaves(c.matrix, k, m);
         if (!leaves.empty() && leaves.size() <= (size_t)m * k) {   // staged like m x k tables
@@ -163,8 +156,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 gf::PermTab t = gf::make_permtab(leaves[i]);
                 memcpy(&dy[i * 8], &t, sizeof(t));
             }
-            HIP_TRY(hipMalloc(&c.d_dytabs, dy.size() * 4));
-            HIP_TRY(hipMemcpy(c.d_dytabs, dy.data(), dy.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(c.d_dytabs.upload(dy.data(), dy.size() * 4));
         }
     }
     // (for m == 0 too: the sorted-plan kernels stage it whatever the code, and a reconstruct of a
@@ -177,8 +169,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 if (t != sidx) d += gf::kTables.log[sidx ^ t];
             dall[sidx] = (uint8_t)(d % 255u);
         }
-        HIP_TRY(hipMalloc(&c.d_dall, FEC_MAX_DECODE_SHARDS));
-        HIP_TRY(hipMemcpy(c.d_dall, dall, FEC_MAX_DECODE_SHARDS, hipMemcpyHostToDevice));
+        HIP_TRY(c.d_dall.upload(dall, FEC_MAX_DECODE_SHARDS));
     }
     auto res = ctx->codes.emplace(key, std::move(c));
     *out = &res.first->second;
@@ -306,17 +297,7 @@ void fec_ctx_destroy(fec_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (auto& kv : ctx->codes) {
-        if (kv.second.d_prows) (void)hipFree(kv.second.d_prows);
-        if (kv.second.d_tabs) (void)hipFree(kv.second.d_tabs);
-        if (kv.second.d_dytabs) (void)hipFree(kv.second.d_dytabs);
-        if (kv.second.d_single) (void)hipFree(kv.second.d_single);
-        if (kv.second.d_single_coef) (void)hipFree(kv.second.d_single_coef);
-        if (kv.second.d_dall) (void)hipFree(kv.second.d_dall);
-        if (kv.second.d_loctab) (void)hipFree(kv.second.d_loctab);
-        if (kv.second.d_loc_carry) (void)hipFree(kv.second.d_loc_carry);
-        if (kv.second.d_lmtab) (void)hipFree(kv.second.d_lmtab);
-    }
+    ctx->codes.clear();   // (each code's device tables free themselves)
     if (ctx->own) (void)hipStreamSynchronize(ctx->own);
     if (ctx->stream && ctx->stream != ctx->own) (void)hipStreamSynchronize(ctx->stream);
     ctx->main.release();
@@ -458,11 +439,7 @@ struct Call {
     int k, m, max_n;           // max_n: the call's largest k + m (the XOR calls: m = 1)
     bool host_ok;              // FEC_HOST / FEC_HOST_PINNED accepted
     int flags;
-    size_t len, nblocks;
-    const uint8_t* data;
-    size_t dbs;
-    const uint8_t** parity;    // m == 0: set to data (never read: no parity slot exists)
-    size_t pbs, ss;
+    Shards s;                  // m == 0: check_call sets parity to data (never read: no parity slot exists)
     bool rs = true;            // the code's tables are needed (not for XOR)
     bool encode = false;       // m == 0 leaves nothing to do
     bool null_arg = false;     // some further pointer the call needs is null
@@ -482,86 +459,90 @@ struct Call {
 };
 constexpr int kRun = 1;
 
-static int check_call(fec_ctx* ctx, const Call& c, Code** code) {
+// The one place where the ABI's pointers lose their const: which region a call writes is stated by
+// fec_hip.h and by the const of the fk::*Args fields that the cores fill from these.
+static uint8_t* region(const uint8_t* p) { return const_cast<uint8_t*>(p); }
+static Shards shards(size_t shard_len, size_t nblocks, const uint8_t* data, size_t data_block_stride,
+                     const uint8_t* parity, size_t parity_block_stride, size_t shard_stride) {
+    return {shard_len,    nblocks,     region(data), data_block_stride, region(parity), parity_block_stride,
+            shard_stride, shard_stride};
+}
+
+static int check_call(fec_ctx* ctx, Call& c, Code** code) {
+    const Shards& s = c.s;
     if (c.k <= 0 || c.m < 0) return FEC_ERR_INV_SHARD_NUM;
     if (c.k + c.m > c.max_n) return FEC_ERR_MAX_SHARD_NUM;
     if (c.max_m >= 0 && c.m > c.max_m) return FEC_ERR_INVALID_ARG;
     if (c.flags != FEC_DEVICE && !(c.host_ok && (c.flags == FEC_HOST || c.flags == FEC_HOST_PINNED)))
         return FEC_ERR_INVALID_ARG;
-    if (c.len == 0) return FEC_ERR_SHARD_NO_DATA;
-    if (c.len > (size_t(1) << 30) || c.out_slots <= 0) return FEC_ERR_INVALID_ARG;
+    if (s.len == 0) return FEC_ERR_SHARD_NO_DATA;
+    if (s.len > (size_t(1) << 30) || c.out_slots <= 0) return FEC_ERR_INVALID_ARG;
     if (c.max_bad < 1 || c.max_bad > FEC_LOCATE_MAX_BAD) return FEC_ERR_INVALID_ARG;
     if (c.wide && (c.mask_words < (size_t)FEC_MASK_WORDS(c.mask_n ? c.mask_n : c.k + c.m) || c.mask_words > 8))
         return FEC_ERR_INVALID_ARG;
     int rc = select_device(ctx);
     if (rc) return rc;
     if (c.rs && (rc = get_code(ctx, c.k, c.m, code))) return rc;
-    if (c.nblocks == 0 || (c.encode && c.m == 0)) return FEC_OK;
-    if (!c.data || c.null_arg || (c.m > 0 && !*c.parity)) return FEC_ERR_INVALID_ARG;
-    if (c.m == 0) *c.parity = c.data;
+    if (s.nblocks == 0 || (c.encode && c.m == 0)) return FEC_OK;
+    if (!s.data || c.null_arg || (c.m > 0 && !s.parity)) return FEC_ERR_INVALID_ARG;
+    if (c.m == 0) c.s.parity = s.data;
     if (c.flags != FEC_DEVICE) return kRun;
-    if ((rc = check_device_layout(c.data, c.dbs, c.ss, c.len))) return rc;
-    if ((rc = check_device_layout(*c.parity, c.pbs, c.ss, c.len))) return rc;
-    if (c.has_out && (rc = check_device_layout(c.out, c.obs, c.ss, c.len))) return rc;
+    if ((rc = check_device_layout(s.data, s.dbs, s.ss, s.len))) return rc;
+    if ((rc = check_device_layout(s.parity, s.pbs, s.ss, s.len))) return rc;
+    if (c.has_out && (rc = check_device_layout(c.out, c.obs, s.ss, s.len))) return rc;
     for (const auto& w : c.words)
         if ((rc = check_device_words(w.a, w.b))) return rc;
     return kRun;
 }
 
 // A recover call is its reconstruct call with an out region, which must be given.
-static void recover_out(Call& c, const uint8_t* out, size_t out_block_stride, int out_slots) {
+static OutRegion recover_out(Call& c, uint8_t* out, size_t out_block_stride, int out_slots) {
     c.null_arg = c.null_arg || !out;
     c.has_out = true, c.out = out, c.obs = out_block_stride, c.out_slots = out_slots;
+    return {out, out_block_stride, (uint32_t)out_slots};
 }
 
 int fec_rs_encode_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
                         size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                         size_t shard_stride, int flags) {
-    const uint8_t* par = parity;
-    Call c{k, m, 256, true, flags, shard_len, nblocks, data, data_block_stride, &par, parity_block_stride, shard_stride};
+    Call c{k, m, 256, true, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.encode = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    if (flags == FEC_DEVICE)
-        return rs_encode_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity,
-                                parity_block_stride, shard_stride);
-    return host_encode(ctx, code, k, m, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
-                       shard_stride, flags == FEC_HOST_PINNED);
+    if (flags == FEC_DEVICE) return rs_encode_device(ctx, code, c.s);
+    return host_encode(ctx, code, k, m, c.s, flags == FEC_HOST_PINNED);
 }
 
 int fec_rs_reconstruct_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
                              size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                              size_t shard_stride, const uint32_t* present_mask, int32_t* block_status, int flags) {
-    Call c{k, m, FEC_MAX_DECODE_SHARDS, true, flags, shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, true, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask;
     c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
     if (flags == FEC_DEVICE)
-        return rs_reconstruct_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity,
-                                     parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err);
-    return host_reconstruct_rs(ctx, code, k, m, shard_len, nblocks, data, data_block_stride, parity,
-                               parity_block_stride, shard_stride, present_mask, block_status, flags == FEC_HOST_PINNED);
+        return rs_reconstruct_device(ctx, code, {c.s, {present_mask, 1, block_status, ctx->d_err}, {}});
+    return host_reconstruct_rs(ctx, code, c.s, present_mask, block_status, flags == FEC_HOST_PINNED);
 }
 
 int fec_rs_recover_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
                          size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                          size_t shard_stride, const uint32_t* present_mask, uint8_t* out, size_t out_block_stride,
                          int out_slots, int32_t* block_status, int flags) {
-    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask;
-    recover_out(c, out, out_block_stride, out_slots);
+    const OutRegion o = recover_out(c, out, out_block_stride, out_slots);
     c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_reconstruct_device(ctx, code, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
-                                 parity, parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err,
-                                 out, out_block_stride, (uint32_t)out_slots);
+    return rs_reconstruct_device(ctx, code, {c.s, {present_mask, 1, block_status, ctx->d_err}, o});
 }
 
 // The wide calls with one mask word and a narrow code are the narrow calls, bytes and errors
@@ -573,8 +554,8 @@ int fec_rs_reconstruct_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
     if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)
         return fec_rs_reconstruct_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
                                         parity_block_stride, shard_stride, present_mask, block_status, flags);
-    Call c{k, m, FEC_MAX_WIDE_SHARDS, true, flags, shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_WIDE_SHARDS, true, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask;
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_mask, block_status};
@@ -582,11 +563,8 @@ int fec_rs_reconstruct_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
     if (flags == FEC_DEVICE)
-        return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
-                                          parity_block_stride, shard_stride, present_mask, mask_words, block_status,
-                                          ctx->d_err);
-    return host_reconstruct_wide(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
-                                 shard_stride, present_mask, mask_words, block_status);
+        return rs_reconstruct_wide_device(ctx, k, m, {c.s, {present_mask, mask_words, block_status, ctx->d_err}, {}});
+    return host_reconstruct_wide(ctx, k, m, c.s, present_mask, mask_words, block_status);
 }
 
 int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
@@ -597,51 +575,46 @@ int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
         return fec_rs_recover_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
                                     parity_block_stride, shard_stride, present_mask, out, out_block_stride, out_slots,
                                     block_status, flags);
-    Call c{k, m, FEC_MAX_WIDE_SHARDS, false, flags, shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_WIDE_SHARDS, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask;
-    recover_out(c, out, out_block_stride, out_slots);
+    const OutRegion o = recover_out(c, out, out_block_stride, out_slots);
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_mask, block_status};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_reconstruct_wide_device(ctx, k, m, shard_len, nblocks, const_cast<uint8_t*>(data), data_block_stride,
-                                      parity, parity_block_stride, shard_stride, present_mask, mask_words,
-                                      block_status, ctx->d_err, out, out_block_stride, (uint32_t)out_slots);
+    return rs_reconstruct_wide_device(ctx, k, m, {c.s, {present_mask, mask_words, block_status, ctx->d_err}, o});
 }
 
 // ---------------------------------------------------------------- verify, reconstruct-some
 int fec_rs_verify_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
                         size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                         size_t shard_stride, int32_t* block_status, uint32_t* mismatch_count, int flags) {
-    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &parity, parity_block_stride,
-           shard_stride};
+    Call c{k, m, 256, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !block_status;
     c.words[0] = {mismatch_count, block_status};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_verify_device(ctx, code, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
-                            shard_stride, block_status, mismatch_count);
+    return rs_verify_device(ctx, code, c.s, block_status, mismatch_count);
 }
 
+// (m == 0: the parity region is neither read nor written)
 int fec_rs_reconstruct_some_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
                                   size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                                   size_t shard_stride, const uint32_t* present_mask, const uint32_t* want_mask,
                                   int32_t* block_status, int flags) {
-    const uint8_t* par = parity;   // (m == 0: neither read nor written)
-    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, shard_len, nblocks, data, data_block_stride, &par,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask;
     c.words[0] = {present_mask, block_status};
     c.words[1] = {want_mask, nullptr};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_reconstruct_some_device(ctx, k, m, shard_len, nblocks, data, data_block_stride,
-                                      const_cast<uint8_t*>(par), parity_block_stride, shard_stride, present_mask,
-                                      want_mask, block_status, ctx->d_err);
+    return rs_reconstruct_some_device(ctx, k, m, c.s, {present_mask, 1, block_status, ctx->d_err}, want_mask);
 }
 
 // ---------------------------------------------------------------- locate
@@ -650,8 +623,8 @@ int fec_rs_locate_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nbl
                         size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                         size_t shard_stride, int32_t* bad_shard, uint32_t* present_out, size_t mask_words,
                         uint32_t* counts, int flags) {
-    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &parity, parity_block_stride,
-           shard_stride};
+    Call c{k, m, 256, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !bad_shard;
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_out, bad_shard};
@@ -659,9 +632,7 @@ int fec_rs_locate_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nbl
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_locate_device(ctx, code, shard_len, nblocks,
-                            {data, data_block_stride, parity, parity_block_stride, shard_stride, bad_shard,
-                             present_out, mask_words, counts});
+    return rs_locate_device(ctx, code, {c.s, bad_shard, present_out, mask_words, counts});
 }
 
 // Up to m/2 corrupt shards per block; m <= 16 (one pass of the scan's 16 rows).
@@ -669,8 +640,8 @@ int fec_rs_locate_multi_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
                               size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                               size_t shard_stride, int max_bad, int32_t* bad_count, uint32_t* present_out,
                               size_t mask_words, uint32_t* counts, int flags) {
-    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &parity, parity_block_stride,
-           shard_stride};
+    Call c{k, m, 256, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !bad_count;
     c.max_m = fk::kLocateMultiRows, c.max_bad = max_bad;
     c.wide = true, c.mask_words = mask_words;
@@ -679,48 +650,40 @@ int fec_rs_locate_multi_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_locate_multi_device(ctx, code, shard_len, nblocks,
-                                  {data, data_block_stride, parity, parity_block_stride, shard_stride, max_bad,
-                                   bad_count, present_out, mask_words, counts});
+    return rs_locate_multi_device(ctx, code, {c.s, max_bad, bad_count, present_out, mask_words, counts});
 }
 
 // ---------------------------------------------------------------- update, encode-idx
-// The two calls differ in the old region alone. The Call's data region is the data folded in (the
-// new version), its out region the old version: the layouts are checked in the order new data,
-// parity, old data.
-static int rs_update_call(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, bool has_old,
-                          const uint8_t* old_data, size_t old_block_stride, const uint8_t* data,
-                          size_t data_block_stride, uint8_t* parity, size_t parity_block_stride, size_t shard_stride,
-                          const uint32_t* mask, size_t mask_words, int flags) {
-    const uint8_t* par = parity;
-    Call c{k, m, 256, false, flags, shard_len, nblocks, data, data_block_stride, &par, parity_block_stride,
-           shard_stride};
+// The two calls differ in the old region alone, which the update call states before it comes here. The
+// Call's data region is the data folded in (the new version), its out region the old version: the
+// layouts are checked in the order new data, parity, old data.
+static int rs_update_call(fec_ctx* ctx, Call& c, const uint32_t* mask, size_t mask_words) {
     c.encode = true;
-    c.null_arg = !mask || (has_old && !old_data);
-    if (has_old) c.has_out = true, c.out = old_data, c.obs = old_block_stride;
-    c.wide = true, c.mask_words = mask_words, c.mask_n = k;
+    c.null_arg = !mask || (c.has_out && !c.out);
+    c.wide = true, c.mask_words = mask_words, c.mask_n = c.k;
     c.words[0] = {mask, nullptr};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_update_device(ctx, code, shard_len, nblocks,
-                            {data, data_block_stride, has_old ? old_data : nullptr, old_block_stride, parity,
-                             parity_block_stride, shard_stride, mask, mask_words});
+    return rs_update_device(ctx, code, {c.s, {region(c.out), c.obs}, mask, mask_words});
 }
 
 int fec_rs_update_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* old_data,
                         size_t old_block_stride, const uint8_t* new_data, size_t new_block_stride, uint8_t* parity,
                         size_t parity_block_stride, size_t shard_stride, const uint32_t* changed_mask,
                         size_t mask_words, int flags) {
-    return rs_update_call(ctx, k, m, shard_len, nblocks, true, old_data, old_block_stride, new_data, new_block_stride,
-                          parity, parity_block_stride, shard_stride, changed_mask, mask_words, flags);
+    Call c{k, m, 256, false, flags,
+           shards(shard_len, nblocks, new_data, new_block_stride, parity, parity_block_stride, shard_stride)};
+    c.has_out = true, c.out = old_data, c.obs = old_block_stride;
+    return rs_update_call(ctx, c, changed_mask, mask_words);
 }
 
 int fec_rs_encode_idx_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
                             size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                             size_t shard_stride, const uint32_t* idx_mask, size_t mask_words, int flags) {
-    return rs_update_call(ctx, k, m, shard_len, nblocks, false, nullptr, 0, data, data_block_stride, parity,
-                          parity_block_stride, shard_stride, idx_mask, mask_words, flags);
+    Call c{k, m, 256, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
+    return rs_update_call(ctx, c, idx_mask, mask_words);
 }
 
 // ---------------------------------------------------------------- ragged batches
@@ -728,34 +691,30 @@ int fec_rs_encode_idx_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t
 int fec_rs_encode_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, const uint8_t* data,
                                size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                                size_t shard_stride, const uint32_t* block_len, int32_t* block_status, int flags) {
-    const uint8_t* par = parity;
-    Call c{k, m, 256, false, flags, max_shard_len, nblocks, data, data_block_stride, &par, parity_block_stride,
-           shard_stride};
+    Call c{k, m, 256, false, flags,
+           shards(max_shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.encode = true;
     c.null_arg = !block_len;
     c.words[0] = {block_len, block_status};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_encode_ragged_device(ctx, code, max_shard_len, nblocks, data, data_block_stride, parity,
-                                   parity_block_stride, shard_stride, block_len, block_status, ctx->d_err);
+    return rs_encode_ragged_device(ctx, code, c.s, block_len, block_status, ctx->d_err);
 }
 
 int fec_rs_reconstruct_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, uint8_t* data,
                                     size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                                     size_t shard_stride, const uint32_t* present_mask, const uint32_t* block_len,
                                     int32_t* block_status, int flags) {
-    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, max_shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags,
+           shards(max_shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask || !block_len;
     c.words[0] = {present_mask, block_status};
     c.words[1] = {block_len, nullptr};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_reconstruct_ragged_device(ctx, code, max_shard_len, nblocks, data, data_block_stride, parity,
-                                        parity_block_stride, shard_stride, present_mask, block_len, block_status,
-                                        ctx->d_err);
+    return rs_reconstruct_ragged_device(ctx, code, {c.s, {present_mask, 1, block_status, ctx->d_err}, {}}, block_len);
 }
 
 int fec_rs_recover_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, const uint8_t* data,
@@ -763,51 +722,42 @@ int fec_rs_recover_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len
                                 size_t shard_stride, const uint32_t* present_mask, const uint32_t* block_len,
                                 uint8_t* out, size_t out_block_stride, int out_slots, int32_t* block_status,
                                 int flags) {
-    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags, max_shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags,
+           shards(max_shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.null_arg = !present_mask || !block_len;
-    recover_out(c, out, out_block_stride, out_slots);
+    const OutRegion o = recover_out(c, out, out_block_stride, out_slots);
     c.words[0] = {present_mask, block_status};
     c.words[1] = {block_len, nullptr};
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
-    return rs_reconstruct_ragged_device(ctx, code, max_shard_len, nblocks, const_cast<uint8_t*>(data),
-                                        data_block_stride, parity, parity_block_stride, shard_stride, present_mask,
-                                        block_len, block_status, ctx->d_err, out, out_block_stride,
-                                        (uint32_t)out_slots);
+    return rs_reconstruct_ragged_device(ctx, code, {c.s, {present_mask, 1, block_status, ctx->d_err}, o}, block_len);
 }
 
 int fec_xor_encode_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, const uint8_t* data,
                          size_t data_block_stride, uint8_t* parity, size_t parity_block_stride, size_t shard_stride,
                          int flags) {
-    const uint8_t* par = parity;
-    Call c{k, 1, 256, true, flags, shard_len, nblocks, data, data_block_stride, &par, parity_block_stride, shard_stride};
+    Call c{k, 1, 256, true, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.rs = false;
     const int rc = check_call(ctx, c, nullptr);
     if (rc != kRun) return rc;
-    if (flags == FEC_DEVICE)
-        return xor_encode_device(ctx, k, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
-                                 shard_stride);
-    return host_encode(ctx, nullptr, k, 1, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
-                       shard_stride, flags == FEC_HOST_PINNED);
+    if (flags == FEC_DEVICE) return xor_encode_device(ctx, k, c.s);
+    return host_encode(ctx, nullptr, k, 1, c.s, flags == FEC_HOST_PINNED);
 }
 
 int fec_xor_reconstruct_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, uint8_t* data,
                               size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
                               size_t shard_stride, const uint32_t* present_mask, int32_t* block_status, int flags) {
-    Call c{k, 1, FEC_MAX_DECODE_SHARDS, true, flags, shard_len, nblocks, data, data_block_stride, &parity,
-           parity_block_stride, shard_stride};
+    Call c{k, 1, FEC_MAX_DECODE_SHARDS, true, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
     c.rs = false;
     c.null_arg = !present_mask;
     c.words[0] = {present_mask, block_status};
     const int rc = check_call(ctx, c, nullptr);
     if (rc != kRun) return rc;
-    if (flags == FEC_DEVICE)
-        return xor_reconstruct_device(ctx, k, shard_len, nblocks, data, data_block_stride, parity,
-                                      parity_block_stride, shard_stride, present_mask, block_status, ctx->d_err);
-    return host_reconstruct_xor(ctx, k, shard_len, nblocks, data, data_block_stride, parity, parity_block_stride,
-                                shard_stride, present_mask, block_status);
+    if (flags == FEC_DEVICE) return xor_reconstruct_device(ctx, k, c.s, {present_mask, 1, block_status, ctx->d_err});
+    return host_reconstruct_xor(ctx, k, c.s, present_mask, block_status);
 }
 
 }  // extern "C"

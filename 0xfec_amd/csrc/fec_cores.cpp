@@ -44,50 +44,54 @@ static int for_slices(size_t nblocks, size_t per_launch, F body) {
 // What EncodeArgs, VerifyArgs and RagEncodeArgs share: the data of the launch's first block and the
 // tables of the pass of up to 16 parity rows from r0.
 template <class Args>
-static void fill_row_pass(Args& a, const Code* code, int r0, const uint8_t* data, size_t dbs, size_t ss) {
-    a.in = data;
-    a.in_bs = dbs;
-    a.ss = ss;
+static void fill_row_pass(Args& a, const Code* code, int r0, const Shards& sl) {
+    a.in = sl.data;
+    a.in_bs = sl.dbs;
+    a.ss = sl.ss;
     a.k = (uint32_t)code->k;
     a.m = (uint32_t)std::min(16, code->m - r0);
     a.tabs = code->d_tabs + (size_t)r0 * code->k * 8;
 }
 
-// The item fields of a flat launch over nb blocks of cps chunks each (shards of len bytes).
+// The item fields of a flat launch over the slice's blocks.
 template <class Args>
-static void fill_flat(Args& a, size_t len, uint32_t cps, size_t nb) {
-    a.len = (uint32_t)len;
-    a.cps = cps;
-    a.total = (uint32_t)(nb * cps);
-    a.div_cps = fk::make_fastdiv(cps);
+static void fill_flat(Args& a, const Shards& sl) {
+    a.len = (uint32_t)sl.len;
+    a.cps = chunks_of(sl.len);
+    a.total = (uint32_t)(sl.nblocks * a.cps);
+    a.div_cps = fk::make_fastdiv(a.cps);
 }
 
 // A launch that starts from the stored parity (SyndromeArgs; UpdateArgs; LocateArgs, which then sets
-// its own m and tables) over blocks [b0, b0 + nb) of a call: the row pass from r0, the parity from
-// that row, the item fields.
-template <class Args, class Par>
-static void fill_syndrome(Args& a, const Code* code, int r0, const uint8_t* data, size_t dbs, Par* parity,
-                          size_t pbs, size_t ss, size_t len, uint32_t cps, size_t b0, size_t nb) {
-    fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
-    a.par = parity + b0 * pbs + (size_t)r0 * ss;
-    a.par_bs = pbs;
-    fill_flat(a, len, cps, nb);
+// its own m and tables) over one slice of a call: the row pass from r0, the parity from that row, the
+// item fields.
+template <class Args>
+static void fill_syndrome(Args& a, const Code* code, int r0, const Shards& sl) {
+    fill_row_pass(a, code, r0, sl);
+    a.par = sl.par(0, r0);
+    a.par_bs = sl.pbs;
+    fill_flat(a, sl);
 }
 
-int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data,
-                     size_t dbs, uint8_t* parity, size_t pbs, size_t ss) {
-    const uint32_t cps = chunks_of(len);
+// The slices of a batch whose launches keep no plan records: sl = s.blocks(b0, nb) for body(sl, b0).
+template <class F>
+static int for_flat_slices(const Shards& s, F body) {
+    return for_slices(s.nblocks, blocks_per_launch(s.nblocks, chunks_of(s.len)),
+                      [&](size_t b0, size_t nb) -> int { return body(s.blocks(b0, nb), b0); });
+}
+
+int rs_encode_device(fec_ctx* ctx, Code* code, const Shards& s) {
     const int k = code->k;
-    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+    return for_flat_slices(s, [&](const Shards& sl, size_t) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
             fk::EncodeArgs a{};
-            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
-            a.out = parity + b0 * pbs + (size_t)r0 * ss;
-            a.out_bs = pbs;
-            fill_flat(a, len, cps, nb);
-            a.dytabs = (r0 == 0 && (int)a.m == code->m) ? code->d_dytabs : nullptr;
-            a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {data, dbs, ss, (uint64_t)k},
-                                           {parity, pbs, ss, (uint64_t)code->m}, len, nblocks);
+            fill_row_pass(a, code, r0, sl);
+            a.out = sl.par(0, r0);
+            a.out_bs = sl.pbs;
+            fill_flat(a, sl);
+            a.dytabs = (r0 == 0 && (int)a.m == code->m) ? code->d_dytabs.p : nullptr;
+            a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {s.data, s.dbs, s.ss, (uint64_t)k},
+                                           {s.parity, s.pbs, s.pss, (uint64_t)code->m}, s.len, s.nblocks);
             if (fk::fixed_encode_applies((uint32_t)k, a.m, a.dytabs != nullptr)) {
                 HIP_TRY(fk::launch_rs_encode_fixed(a, ctx->stream));
                 continue;
@@ -98,64 +102,49 @@ int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const
     });
 }
 
-// What a slice's PlanArgs and ReconArgs hold in the uniform and the ragged reconstruct alike: blocks
-// [b0, b0 + nb) of the call, records of layout `lay` in the stream's workspace, tiles of G blocks.
-struct ReconCall {
-    uint8_t* data;
-    size_t dbs;
-    const uint8_t* parity;
-    size_t pbs, ss, pss;
-    const uint32_t* masks;
-    int32_t* status;
-    int* err;
-    uint8_t* out;
-    size_t out_bs;
-    uint32_t out_slots;
-};
+// What a slice's PlanArgs and ReconArgs hold in the uniform and the ragged reconstruct alike: the
+// slice c of the call, records of layout `lay` in the stream's workspace, tiles of G blocks.
 static void fill_recon_slice(fk::PlanArgs& p, fk::ReconArgs& a, fec_ctx* ctx, const Code* code, const ReconCall& c,
-                             size_t len, uint32_t cps, uint32_t maxe, const fk::PlanLayout& lay, uint32_t G,
-                             size_t b0, size_t nb) {
-    p.masks = c.masks + b0;
+                             uint32_t maxe, const fk::PlanLayout& lay, uint32_t G) {
+    p.masks = c.w.masks;
     p.plans = ctx->work->d_plans;
-    p.status = c.status ? c.status + b0 : nullptr;
-    p.err = c.err;
+    p.status = c.w.status;
+    p.err = c.w.err;
     p.prows = code->d_prows;
     p.k = (uint32_t)code->k;
     p.m = (uint32_t)code->m;
-    p.nblocks = (uint32_t)nb;
+    p.nblocks = (uint32_t)c.s.nblocks;
     p.maxe = maxe;
     p.lay = lay;
-    p.max_out = c.out ? c.out_slots : 0;
+    p.max_out = c.out.base ? c.out.slots : 0;
     p.dall = code->d_dall;   // (read by the sorted plans only)
-    a.data = c.data + b0 * c.dbs;
-    a.parity = c.parity + b0 * c.pbs;
-    a.dbs = c.dbs;
-    a.pbs = c.pbs;
-    a.ss = c.ss;
-    a.pss = c.pss;
+    a.data = c.s.data;
+    a.parity = c.s.parity;
+    a.dbs = c.s.dbs;
+    a.pbs = c.s.pbs;
+    a.ss = c.s.ss;
+    a.pss = c.s.pss;
     a.plans = ctx->work->d_plans;
     a.k = p.k;
-    a.len = (uint32_t)len;
-    a.cps = cps;
-    a.nblocks = (uint32_t)nb;
+    a.len = (uint32_t)c.s.len;
+    a.cps = chunks_of(c.s.len);
+    a.nblocks = p.nblocks;
     a.maxe = maxe;
     a.lay = lay;
     a.g = G;
-    a.ntiles = (uint32_t)((nb + G - 1) / G);
-    a.div_cps = fk::make_fastdiv(cps);
-    a.out = c.out ? c.out + b0 * c.out_bs : nullptr;
-    a.out_bs = c.out_bs;
+    a.ntiles = (uint32_t)((c.s.nblocks + G - 1) / G);
+    a.div_cps = fk::make_fastdiv(a.cps);
+    a.out = c.out.base;
+    a.out_bs = c.out.bs;
 }
 
-int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, uint8_t* data,
-                          size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                          int32_t* status, int* err, uint8_t* out, size_t out_bs, uint32_t out_slots,
-                          size_t pss) {
-    if (pss == 0) pss = ss;
-    if ((ss | pss) >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernels take 32-bit shard strides
+int rs_reconstruct_device(fec_ctx* ctx, Code* code, const ReconCall& call) {
+    const Shards& s = call.s;
+    const OutRegion& out = call.out;
+    if ((s.ss | s.pss) >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernels take 32-bit shard strides
     const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
     const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
-    const uint32_t cps = chunks_of(len);
+    const uint32_t cps = chunks_of(s.len);
     const fk::PlanLayout lay_block = fk::plan_layout(k, maxe), lay_sorted = fk::plan_layout(k, maxe, true);
     // Three forms:
     //  * direct (fec_recover.hip): no plan kernel; single-erasure tables of the code, for calls
@@ -168,13 +157,13 @@ int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, 
     //  * routed (in-place calls of RS(8,12)): a classify pass reduces the masks to one word; the
     //    sorted plans run only if some block has two or more erased data shards, and one kernel
     //    runs the direct body or the wave rebuild by that word (fec_recover.hip).
-    const bool single_slot = out && out_slots == 1;
+    const bool single_slot = out.base && out.slots == 1;
     const bool direct = code->d_single_coef && fk::direct_recon_applies(k, m, cps, single_slot);
     const bool wave = !direct && fk::wave_recon_applies(cps, k, maxe, lay_sorted.stride);
-    const bool routed = wave && !out && code->d_single_coef && !fk::rebuild_k_applies(k, maxe, cps) &&
+    const bool routed = wave && !out.base && code->d_single_coef && !fk::rebuild_k_applies(k, maxe, cps) &&
                         fk::routed_recon_applies(k, m, cps, maxe, lay_sorted.stride);
     const fk::PlanLayout lay = wave ? lay_sorted : lay_block;
-    const size_t per_launch = blocks_per_launch(nblocks, cps, direct ? 0 : lay.stride);
+    const size_t per_launch = blocks_per_launch(s.nblocks, cps, direct ? 0 : lay.stride);
     if (!direct) {
         const int rc = grow_plans(ctx, per_launch * lay.stride);
         if (rc) return rc;
@@ -184,11 +173,10 @@ int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, 
         if (rc) return rc;
     }
     const uint32_t G = fk::pick_tile_blocks(cps, k, maxe, lay);
-    const ReconCall call{data, dbs, parity, pbs, ss, pss, masks, status, err, out, out_bs, out_slots};
-    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+    return for_slices(s.nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
         fk::PlanArgs p{};
         fk::ReconArgs a{};
-        fill_recon_slice(p, a, ctx, code, call, len, cps, maxe, lay, G, b0, nb);
+        fill_recon_slice(p, a, ctx, code, call.blocks(b0, nb), maxe, lay, G);
         a.sorted = wave ? 1u : 0u;
         if (direct || routed) {
             a.masks = p.masks;
@@ -200,8 +188,8 @@ int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, 
             a.single = code->d_single;
             a.single_coef = code->d_single_coef;
             a.single_coef_host = code->single_coef.data();
-            a.sp = fk::decode_store_policy(fk::g_tune.dst_pol, {data, dbs, ss, k}, {parity, pbs, pss, m},
-                                           {out, out_bs, ss, out_slots}, len, nblocks);
+            a.sp = fk::decode_store_policy(fk::g_tune.dst_pol, {s.data, s.dbs, s.ss, k}, {s.parity, s.pbs, s.pss, m},
+                                           {out.base, out.bs, s.ss, out.slots}, s.len, s.nblocks);
         }
         if (direct) {
             HIP_TRY(fk::launch_rs_recover_direct(a, ctx->stream));
@@ -227,28 +215,28 @@ int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, 
 // lay) writes the launch's records into the stream's workspace, then the tile rebuilds from them:
 // `some` false into out (if set) or the data region, true into the data and the parity region.
 template <class Plan>
-static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, size_t len, size_t nblocks, uint8_t* data,
-                            size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, uint8_t* out, size_t out_bs,
-                            bool some, Plan plan) {
-    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
-    const uint32_t cps = chunks_of(len);
+static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, const Shards& s, const OutRegion& out, bool some,
+                            Plan plan) {
+    if (s.ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild kernel takes 32-bit shard strides
+    const uint32_t cps = chunks_of(s.len);
     const fk::WideLayout lay = fk::wide_layout(k, rows);
-    const size_t per_launch = blocks_per_launch(nblocks, cps, lay.stride);
+    const size_t per_launch = blocks_per_launch(s.nblocks, cps, lay.stride);
     const int rc = grow_plans(ctx, per_launch * lay.stride);
     if (rc) return rc;
     uint32_t G, C, TK;
     fk::wide_tile_shape(cps, k, &G, &C, &TK);
-    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+    return for_slices(s.nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+        const Shards sl = s.blocks(b0, nb);
         fk::WideReconArgs a{};
-        a.data = data + b0 * dbs;
-        a.parity = parity + b0 * pbs;
-        a.dbs = dbs;
-        a.pbs = pbs;
-        a.ss = (uint32_t)ss;
+        a.data = sl.data;
+        a.parity = sl.parity;
+        a.dbs = sl.dbs;
+        a.pbs = sl.pbs;
+        a.ss = (uint32_t)sl.ss;
         a.plans = ctx->work->d_plans;
         a.lay = lay;
         a.k = k;
-        a.len = (uint32_t)len;
+        a.len = (uint32_t)sl.len;
         a.cps = cps;
         a.nblocks = (uint32_t)nb;
         a.g = G;
@@ -258,8 +246,8 @@ static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, size_t len,
         a.ntiles = (uint32_t)((nb + G - 1) / G) * a.nctiles;
         a.div_c = fk::make_fastdiv(C);
         a.div_nct = fk::make_fastdiv(a.nctiles);
-        a.out = out ? out + b0 * out_bs : nullptr;
-        a.out_bs = out_bs;
+        a.out = out.blocks(b0).base;
+        a.out_bs = out.bs;
         HIP_TRY(plan(b0, nb, lay));
         HIP_TRY(fk::launch_rs_rebuild_wide(a, some, ctx->stream));
         return FEC_OK;
@@ -268,26 +256,24 @@ static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, size_t len,
 
 // Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
 // up to 256 shards.
-int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
-                               size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
-                               const uint32_t* masks, size_t mask_words, int32_t* status, int* err,
-                               uint8_t* out, size_t out_bs, uint32_t out_slots) {
+int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, const ReconCall& c) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
     uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
-    if (out) rows = std::min(rows, out_slots);
-    return rs_rebuild_tiles(ctx, k, rows, len, nblocks, data, dbs, parity, pbs, ss, out, out_bs, false,
+    if (c.out.base) rows = std::min(rows, c.out.slots);
+    return rs_rebuild_tiles(ctx, k, rows, c.s, c.out, false,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                const DecodeWords w = c.w.blocks(b0);
                                 fk::WidePlanArgs p{};
-                                p.masks = masks + b0 * mask_words;
-                                p.mask_words = (uint32_t)mask_words;
+                                p.masks = w.masks;
+                                p.mask_words = (uint32_t)w.mask_words;
                                 p.plans = ctx->work->d_plans;
-                                p.status = status ? status + b0 : nullptr;
-                                p.err = err;
+                                p.status = w.status;
+                                p.err = w.err;
                                 p.k = k;
                                 p.n = k + m;
                                 p.nblocks = (uint32_t)nb;
                                 p.rows = rows;
-                                p.max_out = out ? out_slots : 0;
+                                p.max_out = c.out.base ? c.out.slots : 0;
                                 p.lay = lay;
                                 p.div_k = fk::make_fastdiv(k);
                                 return fk::launch_rs_plan_wide(p, ctx->stream);
@@ -297,15 +283,13 @@ int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t 
 // Verify (fec_verify.hip): statuses pre-set to 1 and the count to 0 on the stream, then the encode's
 // launches (cut under kMaxItems items, parity rows in passes of 16) with the stored parity folded
 // in: a pass clears the word of a block it finds bad and counts it if no earlier pass had.
-int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
-                     const uint8_t* parity, size_t pbs, size_t ss, int32_t* status, uint32_t* count) {
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 1, nblocks, ctx->stream));
+int rs_verify_device(fec_ctx* ctx, Code* code, const Shards& s, int32_t* status, uint32_t* count) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 1, s.nblocks, ctx->stream));
     if (count) HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
-    const uint32_t cps = chunks_of(len);
-    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+    return for_flat_slices(s, [&](const Shards& sl, size_t b0) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
             fk::VerifyArgs a{};
-            fill_syndrome(a, code, r0, data, dbs, parity, pbs, ss, len, cps, b0, nb);
+            fill_syndrome(a, code, r0, sl);
             a.status = status + b0;
             a.count = count;
             HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
@@ -317,12 +301,12 @@ int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const
 // Update and encode-idx (fec_update.hip; UpdateCall, fec_ctx.hpp, holds a call's regions and masks).
 // The arguments of one launch: blocks [b0, b0 + nb) of the call, the pass of up to 16 parity rows
 // from r0. No device work (fec__selftest_update_slices calls it without one).
-static void fill_update_launch(fk::UpdateArgs& a, const Code* code, int r0, size_t b0, size_t nb, size_t len,
+static void fill_update_launch(fk::UpdateArgs& a, const Code* code, int r0, const Shards& sl, size_t b0,
                                const UpdateCall& u) {
-    fill_syndrome(a, code, r0, u.in, u.in_bs, u.parity, u.pbs, u.ss, len, chunks_of(len), b0, nb);
-    a.old = u.old ? u.old + b0 * u.old_bs : nullptr;
-    a.old_bs = u.old_bs;
-    a.nblocks = (uint32_t)nb;
+    fill_syndrome(a, code, r0, sl);
+    a.old = u.old.blocks(b0).base;
+    a.old_bs = u.old.bs;
+    a.nblocks = (uint32_t)sl.nblocks;
     a.masks = u.masks + b0 * u.mask_words;
     a.mask_words = (uint32_t)u.mask_words;
 }
@@ -330,11 +314,11 @@ static void fill_update_launch(fk::UpdateArgs& a, const Code* code, int r0, size
 // emit(args) for every launch of a call: the encode's cut under kMaxItems items, parity rows in
 // passes of 16 (each pass reads the masked columns again), until one fails.
 template <class F>
-static int update_launches(const Code* code, size_t len, size_t nblocks, const UpdateCall& u, F emit) {
-    return for_slices(nblocks, blocks_per_launch(nblocks, chunks_of(len)), [&](size_t b0, size_t nb) -> int {
+static int update_launches(const Code* code, const UpdateCall& u, F emit) {
+    return for_flat_slices(u.s, [&](const Shards& sl, size_t b0) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
             fk::UpdateArgs a{};
-            fill_update_launch(a, code, r0, b0, nb, len, u);
+            fill_update_launch(a, code, r0, sl, b0, u);
             const int rc = emit(a);
             if (rc) return rc;
         }
@@ -342,8 +326,8 @@ static int update_launches(const Code* code, size_t len, size_t nblocks, const U
     });
 }
 
-int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const UpdateCall& u) {
-    return update_launches(code, len, nblocks, u, [&](const fk::UpdateArgs& a) -> int {
+int rs_update_device(fec_ctx* ctx, const Code* code, const UpdateCall& u) {
+    return update_launches(code, u, [&](const fk::UpdateArgs& a) -> int {
         HIP_TRY(fk::launch_rs_update(a, flat_grid(a.total), ctx->stream));
         return FEC_OK;
     });
@@ -355,12 +339,11 @@ int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks,
 // r0 = 1, 16, 31, ... (a code of one parity row: row 0 alone; of none: no pass). No device work
 // (fec__selftest_locate_slices calls it without one).
 template <class P, class F>
-static int locate_launches(const Code* code, size_t len, size_t nblocks, const LocateCall& c, P pass, F fin) {
-    const uint32_t cps = chunks_of(len);
-    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+static int locate_launches(const Code* code, const LocateCall& c, P pass, F fin) {
+    return for_flat_slices(c.s, [&](const Shards& sl, size_t b0) -> int {
         for (int r0 = 1; code->m > 0 && (r0 == 1 || r0 < code->m); r0 += fk::kLocateRows - 1) {
             fk::LocateArgs a{};
-            fill_syndrome(a, code, 0, c.data, c.dbs, c.parity, c.pbs, c.ss, len, cps, b0, nb);
+            fill_syndrome(a, code, 0, sl);
             a.m = (uint32_t)code->m;
             a.r0 = (uint32_t)r0;
             a.rows = 1u + (uint32_t)std::min(fk::kLocateRows - 1, code->m - r0);
@@ -380,7 +363,7 @@ static int locate_launches(const Code* code, size_t len, size_t nblocks, const L
         f.verdict = c.verdict + b0;
         f.present = c.present ? c.present + b0 * c.mask_words : nullptr;
         f.counts = c.counts;
-        f.nblocks = (uint32_t)nb;
+        f.nblocks = (uint32_t)sl.nblocks;
         f.n = (uint32_t)(code->k + code->m);
         f.mask_words = (uint32_t)c.mask_words;
         return fin(f);
@@ -388,11 +371,11 @@ static int locate_launches(const Code* code, size_t len, size_t nblocks, const L
 }
 
 // Verdicts pre-set to clean and the counts to 0 on the stream, as verify presets its statuses.
-int rs_locate_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateCall& c) {
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c.verdict, fk::kLocateClean, nblocks, ctx->stream));
+int rs_locate_device(fec_ctx* ctx, const Code* code, const LocateCall& c) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c.verdict, fk::kLocateClean, c.s.nblocks, ctx->stream));
     if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 2 * sizeof(uint32_t), ctx->stream));
     return locate_launches(
-        code, len, nblocks, c,
+        code, c,
         [&](const fk::LocateArgs& a) -> int {
             HIP_TRY(fk::launch_rs_locate(a, flat_grid(a.total), ctx->stream));
             return FEC_OK;
@@ -423,16 +406,16 @@ struct LocateMultiSlice {
 // run(slice) for every slice of a call whose workspace is at ws, until one fails. No device work
 // (fec__selftest_locate_multi_slices calls it without one).
 template <class R>
-static int locate_multi_launches(const Code* code, size_t len, size_t nblocks, const LocateMultiCall& c, uint8_t* ws,
-                                 R run) {
-    const uint32_t cps = chunks_of(len);
+static int locate_multi_launches(const Code* code, const LocateMultiCall& c, uint8_t* ws, R run) {
+    const size_t nblocks = c.s.nblocks;
+    const uint32_t cps = chunks_of(c.s.len);
     const uint32_t n = (uint32_t)(code->k + code->m), words = (n + 31) / 32;
     const uint32_t T = fk::locate_multi_radius((uint32_t)code->m, (uint32_t)c.max_bad);
     return for_slices(nblocks, locate_multi_per_launch(nblocks, cps, words), [&](size_t b0, size_t nb) -> int {
         LocateMultiSlice sl{};
         sl.clear = fk::locate_multi_ws_bytes(nb, cps, words);
         fk::LocateMultiScanArgs& a = sl.scan;
-        fill_syndrome(a, code, 0, c.data, c.dbs, c.parity, c.pbs, c.ss, len, cps, b0, nb);   // (m <= 16)
+        fill_syndrome(a, code, 0, c.s.blocks(b0, nb));   // (m <= 16)
         a.bitmap = (uint64_t*)ws;
         fk::LocateMultiSolveArgs& v = sl.solve;
         v.s = a;
@@ -459,14 +442,14 @@ static int locate_multi_launches(const Code* code, size_t len, size_t nblocks, c
 
 // The counts are set to 0 on the stream, as verify presets its count; each slice clears its workspace,
 // which is the stream's (ctx->work), so slices and calls on one stream follow one another in it.
-int rs_locate_multi_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateMultiCall& c) {
-    const uint32_t cps = chunks_of(len);
+int rs_locate_multi_device(fec_ctx* ctx, const Code* code, const LocateMultiCall& c) {
+    const uint32_t cps = chunks_of(c.s.len);
     const uint32_t words = (uint32_t)(code->k + code->m + 31) / 32;
-    const size_t per = locate_multi_per_launch(nblocks, cps, words);
+    const size_t per = locate_multi_per_launch(c.s.nblocks, cps, words);
     const int rc = grow_plans(ctx, fk::locate_multi_ws_bytes(per, cps, words));
     if (rc) return rc;
     if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 2 * sizeof(uint32_t), ctx->stream));
-    return locate_multi_launches(code, len, nblocks, c, ctx->work->d_plans, [&](const LocateMultiSlice& sl) -> int {
+    return locate_multi_launches(code, c, ctx->work->d_plans, [&](const LocateMultiSlice& sl) -> int {
         HIP_TRY(hipMemsetAsync(ctx->work->d_plans, 0, sl.clear, ctx->stream));
         HIP_TRY(fk::launch_rs_locate_multi_scan(sl.scan, flat_grid(sl.scan.total), ctx->stream));
         HIP_TRY(fk::launch_rs_locate_multi_solve(sl.solve, ctx->stream));
@@ -477,18 +460,18 @@ int rs_locate_multi_device(fec_ctx* ctx, const Code* code, size_t len, size_t nb
 
 // Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
 // the wide tile, storing into both regions.
-int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, size_t len, size_t nblocks, uint8_t* data,
-                               size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                               const uint32_t* want, int32_t* status, int* err) {
+int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
+                               const uint32_t* want) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
-    return rs_rebuild_tiles(ctx, k, fk::some_rows(m), len, nblocks, data, dbs, parity, pbs, ss, nullptr, 0, true,
+    return rs_rebuild_tiles(ctx, k, fk::some_rows(m), s, {}, true,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                const DecodeWords w = words.blocks(b0);
                                 fk::SomePlanArgs p{};
-                                p.masks = masks + b0;
+                                p.masks = w.masks;
                                 p.want = want ? want + b0 : nullptr;
                                 p.plans = ctx->work->d_plans;
-                                p.status = status ? status + b0 : nullptr;
-                                p.err = err;
+                                p.status = w.status;
+                                p.err = w.err;
                                 p.k = k;
                                 p.n = k + m;
                                 p.nblocks = (uint32_t)nb;
@@ -506,19 +489,18 @@ static uint32_t ragged_encode_blocks(uint32_t cps_max) {
     return fk::rag_clamp_blocks(want, cps_max);
 }
 
-int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, const uint8_t* data,
-                            size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* lens,
-                            int32_t* status, int* err) {
-    const uint32_t cps = chunks_of(max_len);
+int rs_encode_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,
+                            int* err) {
+    const uint32_t cps = chunks_of(s.len);
     const uint32_t G = ragged_encode_blocks(cps);
-    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
+    return for_flat_slices(s, [&](const Shards& sl, size_t b0) -> int {
         for (int r0 = 0; r0 < code->m; r0 += 16) {
             fk::RagEncodeArgs a{};
-            fill_row_pass(a, code, r0, data + b0 * dbs, dbs, ss);
-            a.out = parity + b0 * pbs + (size_t)r0 * ss;
-            a.out_bs = pbs;
-            a.max_len = (uint32_t)max_len;
-            a.nblocks = (uint32_t)nb;
+            fill_row_pass(a, code, r0, sl);
+            a.out = sl.par(0, r0);
+            a.out_bs = sl.pbs;
+            a.max_len = (uint32_t)sl.len;
+            a.nblocks = (uint32_t)sl.nblocks;
             a.g = G;
             a.nwin = fk::rag_windows(G, cps);
             a.lens = lens + b0;
@@ -533,20 +515,18 @@ int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nbl
 
 // Plans in block order by rs_plan_kernel (they do not depend on the length), then the ragged tile
 // rebuild, which also overrides the status of oversize blocks.
-int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, uint8_t* data,
-                                 size_t dbs, const uint8_t* parity, size_t pbs, size_t ss,
-                                 const uint32_t* masks, const uint32_t* lens, int32_t* status, int* err,
-                                 uint8_t* out, size_t out_bs, uint32_t out_slots) {
-    if (ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild takes 32-bit shard strides
+int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, const ReconCall& call, const uint32_t* lens) {
+    const Shards& s = call.s;
+    if (s.ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild takes 32-bit shard strides
     const uint32_t k = (uint32_t)code->k, m = (uint32_t)code->m;
     const uint32_t maxe = std::max<uint32_t>(1, std::min(k, m));
-    const uint32_t cps = chunks_of(max_len);
+    const uint32_t cps = chunks_of(s.len);
     const fk::PlanLayout lay = fk::plan_layout(k, maxe);
-    const size_t per_launch = blocks_per_launch(nblocks, cps, lay.stride);
+    const size_t per_launch = blocks_per_launch(s.nblocks, cps, lay.stride);
     const int rc = grow_plans(ctx, per_launch * lay.stride);
     if (rc) return rc;
     // rows a block can need: the plan kernel gives a block with more erasures than slots no rows
-    const uint32_t rows = out ? std::min(maxe, out_slots) : maxe;
+    const uint32_t rows = call.out.base ? std::min(maxe, call.out.slots) : maxe;
     // Blocks per tile: as the encode's, so that a tile of full-length blocks fills one window, within
     // what LDS holds. (pick_tile_blocks, the uniform tile form's choice, looks for the fewest blocks
     // that fill the lanes of a full-length tile: RS(20,30) 3. A ragged tile has fewer items than
@@ -556,15 +536,14 @@ int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_
     const int forced = fk::g_tune.rag_g;
     uint32_t G = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps);
     G = fk::rag_clamp_blocks(std::min(G, fk::rag_recon_max_blocks(k, rows, lay)), cps);
-    const ReconCall call{data, dbs, parity, pbs, ss, ss, masks, status, err, out, out_bs, out_slots};
-    return for_slices(nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+    return for_slices(s.nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
         fk::PlanArgs p{};
         fk::RagReconArgs ra{};
-        fill_recon_slice(p, ra.r, ctx, code, call, max_len, cps, maxe, lay, G, b0, nb);
+        fill_recon_slice(p, ra.r, ctx, code, call.blocks(b0, nb), maxe, lay, G);
         ra.r.status = p.status;
-        ra.r.err = err;
+        ra.r.err = p.err;
         ra.lens = lens + b0;
-        ra.max_len = (uint32_t)max_len;
+        ra.max_len = (uint32_t)s.len;
         ra.nwin = fk::rag_windows(G, cps);
         ra.rows = rows;
         HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
@@ -573,49 +552,91 @@ int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_
     });
 }
 
-// The XOR calls' launch arguments for blocks [b0, b0 + nb): the encode's, and the in-place
-// reconstruct's (data rebuilt where it lies, parity read).
-static fk::XorArgs xor_slice(int k, size_t len, uint32_t cps, const uint8_t* in, size_t in_bs, uint8_t* out,
-                             size_t out_bs, size_t ss, size_t b0, size_t nb) {
+// The XOR calls' launch arguments for one slice: the encode's, or the in-place reconstruct's (data
+// rebuilt where it lies, parity read).
+static fk::XorArgs xor_slice(int k, const Shards& sl, bool encode) {
     fk::XorArgs a{};
-    a.in = in + b0 * in_bs;
-    a.out = out + b0 * out_bs;
-    a.in_bs = in_bs;
-    a.out_bs = out_bs;
-    a.ss = ss;
+    a.in = sl.data;
+    a.out = encode ? sl.parity : sl.data;
+    a.in_bs = sl.dbs;
+    a.out_bs = encode ? sl.pbs : sl.dbs;
+    a.ss = sl.ss;
     a.k = (uint32_t)k;
-    fill_flat(a, len, cps, nb);
+    fill_flat(a, sl);
     return a;
 }
 
-int xor_encode_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
-                      uint8_t* parity, size_t pbs, size_t ss) {
-    const uint32_t cps = chunks_of(len);
-    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
-        const fk::XorArgs a = xor_slice(k, len, cps, data, dbs, parity, pbs, ss, b0, nb);
+int xor_encode_device(fec_ctx* ctx, int k, const Shards& s) {
+    return for_flat_slices(s, [&](const Shards& sl, size_t) -> int {
+        const fk::XorArgs a = xor_slice(k, sl, true);
         HIP_TRY(fk::launch_xor_encode(a, flat_grid(a.total), ctx->stream));
         return FEC_OK;
     });
 }
 
-int xor_reconstruct_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                           const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                           int32_t* status, int* err) {
-    const uint32_t cps = chunks_of(len);
-    return for_slices(nblocks, blocks_per_launch(nblocks, cps), [&](size_t b0, size_t nb) -> int {
-        fk::XorArgs a = xor_slice(k, len, cps, data, dbs, data, dbs, ss, b0, nb);
-        a.parity = parity + b0 * pbs;
-        a.par_bs = pbs;
-        a.masks = masks + b0;
-        a.status = status ? status + b0 : nullptr;
-        a.err = err;
-        a.nblocks = (uint32_t)nb;
+int xor_reconstruct_device(fec_ctx* ctx, int k, const Shards& s, const DecodeWords& words) {
+    return for_flat_slices(s, [&](const Shards& sl, size_t b0) -> int {
+        const DecodeWords w = words.blocks(b0);
+        fk::XorArgs a = xor_slice(k, sl, false);
+        a.parity = sl.parity;
+        a.par_bs = sl.pbs;
+        a.masks = w.masks;
+        a.status = w.status;
+        a.err = w.err;
+        a.nblocks = (uint32_t)sl.nblocks;
         HIP_TRY(fk::launch_xor_reconstruct(a, flat_grid(a.total), ctx->stream));
         return FEC_OK;
     });
 }
 
+// A Code for the self-tests below, whose tables are fake addresses: it forgets them before its owners
+// would free them.
+struct FakeCode : Code {
+    ~FakeCode() { d_tabs.p = d_loc_carry.p = d_lmtab.p = nullptr, d_loctab.p = nullptr; }
+};
+
 extern "C" {
+
+// Internal self-test (not part of the public ABI, no device needed): blocks() of Shards, OutRegion and
+// DecodeWords (fec_ctx.hpp), the one place where a region is moved to a launch's or a chunk's first
+// block. A decode call of B = 1000 blocks whose strides all differ (ss != pss, dbs != pbs != out.bs,
+// 3 mask words), cut at (b0, nb) = (0, 1), (0, B), (7, 1), (B - 1, 1): the data, parity, out, mask and
+// status bases move by b0 times their own stride, nblocks is nb, and nothing else changes (the sticky
+// error word and the slot count among it). 0 on success, else 100 * (cut index + 1) + the failing field.
+int fec__selftest_batch_slices(void) {
+    const size_t B = 1000, W = 3;
+    const uintptr_t d0 = uintptr_t(1) << 40, p0 = uintptr_t(2) << 40, o0 = uintptr_t(3) << 40, m0 = uintptr_t(4) << 40,
+                    st0 = uintptr_t(5) << 40, e0 = uintptr_t(6) << 40;
+    const size_t len = 70000, dbs = 350128, pbs = 1400352, ss = 70016, pss = 70048, obs = 140064;
+    const ReconCall c{{len, B, (uint8_t*)d0, dbs, (uint8_t*)p0, pbs, ss, pss},
+                      {(const uint32_t*)m0, W, (int32_t*)st0, (int*)e0},
+                      {(uint8_t*)o0, obs, 2}};
+    const size_t cuts[][2] = {{0, 1}, {0, B}, {7, 1}, {B - 1, 1}};
+    int fail = 0;
+    for (auto& cut : cuts) {
+        fail += 100;
+        const size_t b0 = cut[0], nb = cut[1];
+        const ReconCall g = c.blocks(b0, nb);
+        if ((uintptr_t)g.s.data != d0 + b0 * dbs) return fail + 1;
+        if ((uintptr_t)g.s.parity != p0 + b0 * pbs) return fail + 2;
+        if (g.s.nblocks != nb) return fail + 3;
+        if (g.s.len != len || g.s.dbs != dbs || g.s.pbs != pbs || g.s.ss != ss || g.s.pss != pss) return fail + 4;
+        if ((uintptr_t)g.out.base != o0 + b0 * obs) return fail + 5;
+        if (g.out.bs != obs || g.out.slots != 2) return fail + 6;
+        if ((uintptr_t)g.w.masks != m0 + b0 * W * 4 || g.w.mask_words != W) return fail + 7;
+        if ((uintptr_t)g.w.status != st0 + b0 * 4) return fail + 8;
+        if ((uintptr_t)g.w.err != e0) return fail + 9;
+        // a shard of the slice is that shard of the call
+        if (g.s.shard(0, 4) != c.s.shard(b0, 4) || g.s.par(0, 3) != c.s.par(b0, 3)) return fail + 10;
+        if ((uintptr_t)c.s.par(b0, 3) != p0 + b0 * pbs + 3 * pss) return fail + 11;
+    }
+    // no out region and no statuses: none in any slice
+    ReconCall n = c;
+    n.out = {};
+    n.w.status = nullptr;
+    const ReconCall g = n.blocks(7, 1);
+    return g.out.base || g.w.status ? 1 : 0;
+}
 
 // Internal self-test (not part of the public ABI, no device needed): the launches of an update call
 // that the launch limit cuts. k = 5, m = 20, 70 000-byte shards (4375 chunks), one block more than
@@ -630,18 +651,17 @@ int fec__selftest_update_slices(void) {
     const size_t ss = 70016, in_bs = k * ss + 48, old_bs = k * ss + 16, pbs = m * ss + 32;
     const uintptr_t in0 = uintptr_t(1) << 40, old0 = uintptr_t(2) << 40, par0 = uintptr_t(3) << 40,
                     mask0 = uintptr_t(4) << 40, tab0 = uintptr_t(5) << 40;
-    Code code;
+    FakeCode code;
     code.k = k;
     code.m = m;
-    code.d_tabs = (uint32_t*)tab0;
-    const UpdateCall u{(const uint8_t*)in0, in_bs, (const uint8_t*)old0, old_bs, (uint8_t*)par0, pbs, ss,
+    code.d_tabs.p = (uint32_t*)tab0;
+    const UpdateCall u{{L, B, (uint8_t*)in0, in_bs, (uint8_t*)par0, pbs, ss, ss}, {(uint8_t*)old0, old_bs},
                        (const uint32_t*)mask0, W};
     std::vector<fk::UpdateArgs> got;
-    const int rc = update_launches(&code, L, B, u, [&](const fk::UpdateArgs& a) -> int {
+    const int rc = update_launches(&code, u, [&](const fk::UpdateArgs& a) -> int {
         got.push_back(a);
         return FEC_OK;
     });
-    code.d_tabs = nullptr;
     if (rc != FEC_OK || got.size() != 4) return 2;
     for (size_t i = 0; i < 4; ++i) {
         const fk::UpdateArgs& a = got[i];
@@ -658,11 +678,9 @@ int fec__selftest_update_slices(void) {
     }
     // encode-idx: no old region in any launch
     UpdateCall e = u;
-    e.old = nullptr;
+    e.old = {};
     fk::UpdateArgs a{};
-    code.d_tabs = (uint32_t*)tab0;
-    fill_update_launch(a, &code, 16, per, 1, L, e);
-    code.d_tabs = nullptr;
+    fill_update_launch(a, &code, 16, e.s.blocks(per, 1), per, e);
     if (a.old != nullptr || (uintptr_t)a.in != in0 + per * in_bs) return 3;
     return 0;
 }
@@ -689,18 +707,18 @@ int fec__selftest_locate_slices(void) {
     for (int m : ms) {
         const int base = 1000 * ++mi;
         const size_t pbs = (size_t)m * ss + 32;
-        Code code;
+        FakeCode code;
         code.k = k;
         code.m = m;
-        code.d_tabs = (uint32_t*)tab0;
-        code.d_loctab = (uint8_t*)loc0;
-        const LocateCall c{(const uint8_t*)in0, dbs, (const uint8_t*)par0, pbs, ss, (int32_t*)ver0,
+        code.d_tabs.p = (uint32_t*)tab0;
+        code.d_loctab.p = (uint8_t*)loc0;
+        const LocateCall c{{L, B, (uint8_t*)in0, dbs, (uint8_t*)par0, pbs, ss, ss}, (int32_t*)ver0,
                            (uint32_t*)mask0, W, (uint32_t*)cnt0};
         std::vector<fk::LocateArgs> got;
         std::vector<fk::LocateFinArgs> fins;
         std::vector<size_t> fin_after;   // launches emitted before each finalize
         const int rc = locate_launches(
-            &code, L, B, c,
+            &code, c,
             [&](const fk::LocateArgs& a) -> int {
                 got.push_back(a);
                 return FEC_OK;
@@ -710,8 +728,6 @@ int fec__selftest_locate_slices(void) {
                 fin_after.push_back(got.size());
                 return FEC_OK;
             });
-        code.d_tabs = nullptr;
-        code.d_loctab = nullptr;
         const size_t np = (size_t)want_passes[mi - 1];
         if (rc != FEC_OK || got.size() != 2 * np || fins.size() != 2) return base + 2;
         for (size_t i = 0; i < got.size(); ++i) {
@@ -738,14 +754,14 @@ int fec__selftest_locate_slices(void) {
         }
     }
     // no masks asked for: none in any finalize
-    Code code;
+    FakeCode code;
     code.k = k;
     code.m = 2;
-    code.d_tabs = (uint32_t*)tab0;
-    const LocateCall c{(const uint8_t*)in0, dbs, (const uint8_t*)par0, 2 * ss, ss, (int32_t*)ver0, nullptr, W, nullptr};
+    code.d_tabs.p = (uint32_t*)tab0;
+    LocateCall c{{L, B, (uint8_t*)in0, dbs, (uint8_t*)par0, 2 * ss, ss, ss}, (int32_t*)ver0, nullptr, W, nullptr};
     int bad = 0;
     (void)locate_launches(
-        &code, L, B, c, [&](const fk::LocateArgs&) -> int { return FEC_OK; },
+        &code, c, [&](const fk::LocateArgs&) -> int { return FEC_OK; },
         [&](const fk::LocateFinArgs& f) -> int {
             if (f.present || f.counts) ++bad;
             return FEC_OK;
@@ -756,17 +772,16 @@ int fec__selftest_locate_slices(void) {
     const uintptr_t car0 = uintptr_t(9) << 40;
     code.k = 130;
     code.m = 40;
-    code.d_tabs = (uint32_t*)tab0;
-    code.d_loc_carry = (uint32_t*)car0;
+    code.d_loc_carry.p = (uint32_t*)car0;
+    c.s.len = 16, c.s.nblocks = 1;
     std::vector<fk::LocateArgs> got;
     (void)locate_launches(
-        &code, 16, 1, c,
+        &code, c,
         [&](const fk::LocateArgs& a) -> int {
             got.push_back(a);
             return FEC_OK;
         },
         [&](const fk::LocateFinArgs&) -> int { return FEC_OK; });
-    code.d_tabs = code.d_loc_carry = nullptr;
     if (got.size() != 3 || (uintptr_t)got[0].tabs0 != tab0 || (uintptr_t)got[0].tabs != tab0 + 130 * 8 * 4) return 4;
     for (size_t p = 1; p < 3; ++p)
         if ((uintptr_t)got[p].tabs0 != car0 + (p - 1) * 16 * 130 * 8 * 4 ||
@@ -799,19 +814,18 @@ int fec__selftest_locate_multi_slices(void) {
         const size_t per = std::min<size_t>(kMaxItems / cps, (kPlanBytes - 64) / ((words + 1) * 4 + (cps + 7) / 8));
         const size_t B = per + 1, dbs = k * ss + 48, pbs = (size_t)m * ss + 32;
         if (per >= (size_t)(kMaxItems / cps)) return base + 1;   // the workspace is the tighter limit here
-        Code code;
+        FakeCode code;
         code.k = k;
         code.m = m;
-        code.d_tabs = (uint32_t*)tab0;
-        code.d_lmtab = (uint32_t*)lm0;
-        const LocateMultiCall c{(const uint8_t*)in0, dbs, (const uint8_t*)par0, pbs, ss, cd[2], (int32_t*)out0,
+        code.d_tabs.p = (uint32_t*)tab0;
+        code.d_lmtab.p = (uint32_t*)lm0;
+        const LocateMultiCall c{{L, B, (uint8_t*)in0, dbs, (uint8_t*)par0, pbs, ss, ss}, cd[2], (int32_t*)out0,
                                 (uint32_t*)mask0, W, (uint32_t*)cnt0};
         std::vector<LocateMultiSlice> got;
-        const int rc = locate_multi_launches(&code, L, B, c, (uint8_t*)ws0, [&](const LocateMultiSlice& sl) -> int {
+        const int rc = locate_multi_launches(&code, c, (uint8_t*)ws0, [&](const LocateMultiSlice& sl) -> int {
             got.push_back(sl);
             return FEC_OK;
         });
-        code.d_tabs = code.d_lmtab = nullptr;
         if (rc != FEC_OK || got.size() != 2) return base + 2;
         for (size_t s = 0; s < 2; ++s) {
             const LocateMultiSlice& sl = got[s];
@@ -843,11 +857,12 @@ int fec__selftest_locate_multi_slices(void) {
     Code code;
     code.k = 5;
     code.m = 4;
-    const LocateMultiCall c{(const uint8_t*)in0, 128, (const uint8_t*)par0, 64, 16, 1, (int32_t*)out0, nullptr, 1, nullptr};
     const size_t per = (kPlanBytes - 64) / 9, B = 2 * per + 5;
+    const LocateMultiCall c{{16, B, (uint8_t*)in0, 128, (uint8_t*)par0, 64, 16, 16}, 1, (int32_t*)out0, nullptr, 1,
+                            nullptr};
     size_t slices = 0, blocks = 0;
     int bad = 0;
-    (void)locate_multi_launches(&code, 16, B, c, (uint8_t*)ws0, [&](const LocateMultiSlice& sl) -> int {
+    (void)locate_multi_launches(&code, c, (uint8_t*)ws0, [&](const LocateMultiSlice& sl) -> int {
         if (sl.fin.present || sl.fin.counts || sl.solve.T != 1 || sl.clear > kPlanBytes) ++bad;
         if (sl.scan.total != sl.fin.nblocks || (uintptr_t)sl.scan.in != in0 + blocks * 128) ++bad;
         ++slices, blocks += sl.fin.nblocks;

@@ -14,19 +14,82 @@
 
 #pragma GCC visibility push(hidden)
 
+// One device allocation that frees itself: move-only, null until upload() fills it.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    // hipMalloc of `bytes` and a host-to-device hipMemcpy of them (null stream) from src.
+    hipError_t upload(const void* src, size_t bytes) {
+        const hipError_t e = hipMalloc(&p, bytes);
+        return e != hipSuccess ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    }
+    operator T*() const { return p; }
+};
+
 struct Code {
     int k = 0, m = 0;
     std::vector<uint8_t> matrix;   // n x k
-    uint8_t* d_prows = nullptr;    // m x k
-    uint32_t* d_tabs = nullptr;    // m x k PermTabs
-    uint32_t* d_dytabs = nullptr;  // dyadic codes: leaf PermTabs of the split-recursive encode
-    uint32_t* d_single = nullptr;  // single-erasure decode tables (fk::direct_table_words), when small
-    uint32_t* d_single_coef = nullptr;   // their coefficient bytes, (k*m) rows of ceil(k/4) dwords
+    DevBuf<uint8_t> d_prows;       // m x k
+    DevBuf<uint32_t> d_tabs;       // m x k PermTabs
+    DevBuf<uint32_t> d_dytabs;     // dyadic codes: leaf PermTabs of the split-recursive encode
+    DevBuf<uint32_t> d_single;     // single-erasure decode tables (fk::direct_table_words), when small
+    DevBuf<uint32_t> d_single_coef;      // their coefficient bytes, (k*m) rows of ceil(k/4) dwords
     std::vector<uint32_t> single_coef;   // host copy
-    uint8_t* d_dall = nullptr;     // n bytes: sum_{t != s} log(s ^ t) mod 255 (sorted plans)
-    uint8_t* d_loctab = nullptr;   // m > 0: the locate call's table (fec_locate.hpp locate_table)
-    uint32_t* d_loc_carry = nullptr;   // k > 128, m > 16: PermTabs of locate's later passes, a slab per pass
-    uint32_t* d_lmtab = nullptr;   // 1 <= m <= 16: the locate-multi call's table (fec_locate_multi.hpp)
+    DevBuf<uint8_t> d_dall;        // n bytes: sum_{t != s} log(s ^ t) mod 255 (sorted plans)
+    DevBuf<uint8_t> d_loctab;      // m > 0: the locate call's table (fec_locate.hpp locate_table)
+    DevBuf<uint32_t> d_loc_carry;  // k > 128, m > 16: PermTabs of locate's later passes, a slab per pass
+    DevBuf<uint32_t> d_lmtab;      // 1 <= m <= 16: the locate-multi call's table (fec_locate_multi.hpp)
+};
+
+// The shards of one batch call, or of the blocks of it that one launch or one host chunk takes.
+struct Shards {
+    size_t len, nblocks;   // bytes per shard (ragged calls: max_shard_len), blocks
+    uint8_t* data;         // data shard j of block b at data + b * dbs + j * ss
+    size_t dbs;
+    uint8_t* parity;       // parity shard r of block b at parity + b * pbs + r * pss
+    size_t pbs;
+    size_t ss, pss;        // pss == ss in every ABI layout; the host path's decode stage is parity-major
+                           // (only the narrow reconstruct's kernels take a parity stride of their own)
+    uint8_t* shard(size_t b, size_t j) const { return data + b * dbs + j * ss; }
+    uint8_t* par(size_t b, size_t r) const { return parity + b * pbs + r * pss; }
+    // The same batch, blocks [b0, b0 + nb).
+    Shards blocks(size_t b0, size_t nb) const {
+        Shards s = *this;
+        s.nblocks = nb;
+        s.data += b0 * dbs;
+        s.parity += b0 * pbs;
+        return s;
+    }
+};
+
+// The out region of a recover call (`slots` shards per block, ss apart), or none; the update call's
+// old data.
+struct OutRegion {
+    uint8_t* base = nullptr;
+    size_t bs = 0;
+    uint32_t slots = 0;
+    OutRegion blocks(size_t b0) const { return {base ? base + b0 * bs : nullptr, bs, slots}; }
+};
+
+// The word arrays of a decode: mask_words present-mask words and a status (may be null) per block, and
+// the sticky error word of the whole call.
+struct DecodeWords {
+    const uint32_t* masks;
+    size_t mask_words;
+    int32_t* status;
+    int* err;
+    DecodeWords blocks(size_t b0) const {
+        return {masks + b0 * mask_words, mask_words, status ? status + b0 : nullptr, err};
+    }
 };
 
 // Bytes of staged shards per FEC_HOST chunk (x2 buffers, in and out).
@@ -131,85 +194,61 @@ int grow_masks(fec_ctx* ctx, size_t n);
 
 // ---------------------------------------------------------------- fec_cores.cpp: device-memory cores
 // Each enqueues one call's launches on ctx->stream, with ctx->work as their scratch.
-int rs_encode_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
-                     uint8_t* parity, size_t pbs, size_t ss);
-int rs_reconstruct_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                          const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, int32_t* status,
-                          int* err, uint8_t* out = nullptr, size_t out_bs = 0, uint32_t out_slots = 0,
-                          size_t pss = 0);
-int rs_reconstruct_wide_device(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                               const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                               size_t mask_words, int32_t* status, int* err, uint8_t* out = nullptr,
-                               size_t out_bs = 0, uint32_t out_slots = 0);
-int rs_verify_device(fec_ctx* ctx, Code* code, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
-                     const uint8_t* parity, size_t pbs, size_t ss, int32_t* status, uint32_t* count);
-// Update and encode-idx (fec_update.hip): the regions and masks of one call. `in` is the data folded
-// in (update: the new version), `old` the old version (encode-idx: null).
+int rs_encode_device(fec_ctx* ctx, Code* code, const Shards& s);
+// Reconstruct (no out region: in place in the data region) and recover.
+struct ReconCall {
+    Shards s;
+    DecodeWords w;
+    OutRegion out;
+    ReconCall blocks(size_t b0, size_t nb) const { return {s.blocks(b0, nb), w.blocks(b0), out.blocks(b0)}; }
+};
+int rs_reconstruct_device(fec_ctx* ctx, Code* code, const ReconCall& c);
+int rs_reconstruct_wide_device(fec_ctx* ctx, int k, int m, const ReconCall& c);
+int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, const ReconCall& c, const uint32_t* lens);
+int rs_verify_device(fec_ctx* ctx, Code* code, const Shards& s, int32_t* status, uint32_t* count);
+// Update and encode-idx (fec_update.hip): s.data is the data folded in (update: the new version),
+// `old` the old version (encode-idx: none).
 struct UpdateCall {
-    const uint8_t* in;
-    size_t in_bs;
-    const uint8_t* old;
-    size_t old_bs;
-    uint8_t* parity;
-    size_t pbs, ss;
+    Shards s;
+    OutRegion old;
     const uint32_t* masks;
     size_t mask_words;
 };
-int rs_update_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const UpdateCall& u);
-// Locate (fec_locate.hip): the regions and outputs of one call (present and counts may be null).
+int rs_update_device(fec_ctx* ctx, const Code* code, const UpdateCall& u);
+// Locate (fec_locate.hip): the outputs of one call (present and counts may be null).
 struct LocateCall {
-    const uint8_t* data;
-    size_t dbs;
-    const uint8_t* parity;
-    size_t pbs, ss;
+    Shards s;
     int32_t* verdict;
     uint32_t* present;
     size_t mask_words;
     uint32_t* counts;
 };
-int rs_locate_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateCall& c);
-// Locate-multi (fec_locate_multi.hip): the regions and outputs of one call (present and counts may be
-// null), m <= 16.
+int rs_locate_device(fec_ctx* ctx, const Code* code, const LocateCall& c);
+// Locate-multi (fec_locate_multi.hip): the outputs of one call (present and counts may be null),
+// m <= 16.
 struct LocateMultiCall {
-    const uint8_t* data;
-    size_t dbs;
-    const uint8_t* parity;
-    size_t pbs, ss;
+    Shards s;
     int max_bad;
     int32_t* bad_count;
     uint32_t* present;
     size_t mask_words;
     uint32_t* counts;
 };
-int rs_locate_multi_device(fec_ctx* ctx, const Code* code, size_t len, size_t nblocks, const LocateMultiCall& c);
-int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                               uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, const uint32_t* want,
-                               int32_t* status, int* err);
-int rs_encode_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, const uint8_t* data,
-                            size_t dbs, uint8_t* parity, size_t pbs, size_t ss, const uint32_t* lens,
-                            int32_t* status, int* err);
-int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, size_t max_len, size_t nblocks, uint8_t* data,
-                                 size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                                 const uint32_t* lens, int32_t* status, int* err, uint8_t* out = nullptr,
-                                 size_t out_bs = 0, uint32_t out_slots = 0);
-int xor_encode_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
-                      uint8_t* parity, size_t pbs, size_t ss);
-int xor_reconstruct_device(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                           const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, int32_t* status,
-                           int* err);
+int rs_locate_multi_device(fec_ctx* ctx, const Code* code, const LocateMultiCall& c);
+int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, const Shards& s, const DecodeWords& w,
+                               const uint32_t* want);
+int rs_encode_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,
+                            int* err);
+int xor_encode_device(fec_ctx* ctx, int k, const Shards& s);
+int xor_reconstruct_device(fec_ctx* ctx, int k, const Shards& s, const DecodeWords& w);
 
 // ---------------------------------------------------------------- fec_host.cpp: host-resident path
 // Encode (RS when code != nullptr, else XOR(k, 1)): host data -> host parity.
-int host_encode(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nblocks, const uint8_t* data, size_t dbs,
-                uint8_t* parity, size_t pbs, size_t ss, bool pinned);
-int host_reconstruct_rs(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nblocks, uint8_t* data,
-                        size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                        int32_t* block_status, bool pinned);
-int host_reconstruct_xor(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                         const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                         int32_t* block_status);
-int host_reconstruct_wide(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                          const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, size_t mask_words,
+int host_encode(fec_ctx* ctx, Code* code, int k, int m, const Shards& s, bool pinned);
+int host_reconstruct_rs(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* masks, int32_t* block_status,
+                        bool pinned);
+int host_reconstruct_xor(fec_ctx* ctx, int k, const Shards& s, const uint32_t* masks, int32_t* block_status);
+int host_reconstruct_wide(fec_ctx* ctx, int k, int m, const Shards& s, const uint32_t* masks, size_t mask_words,
                           int32_t* block_status);
 // Free every buffer of the set and forget it (pointers null, capacities 0), whatever a free
 // returns; the first failure, or hipSuccess. The set's events stay.

@@ -133,19 +133,21 @@ static bool dense_span(size_t nb, size_t cols, size_t bs, size_t ss, size_t len)
     return span_bytes(nb, cols, bs, ss, len) * 4 <= nb * cols * len * 5;
 }
 
-// Caller's columns [0, cols) of nb blocks toward the device stage [nb][st_bs/st_ss], on stream
+// The data columns [0, cols) of the caller's blocks `src` toward the device stage `st`, on stream
 // `up`: when the span of all span_cols >= cols columns is dense, one linear DMA of it into `raw`
 // (a few unneeded columns ride along: one linear DMA beats narrow 2D rows) and *repack = true (the
 // kernel stream then runs pinned_repack); else one 2D DMA per column straight into the stage.
-static int pinned_up(hipStream_t up, uint8_t* stage, size_t st_bs, size_t st_ss, const uint8_t* src, size_t bs,
-                     size_t ss, size_t nb, size_t cols, size_t len, uint8_t* raw, size_t span_cols, bool* repack) {
-    *repack = dense_span(nb, span_cols, bs, ss, len);
+static int pinned_up(hipStream_t up, const Shards& st, const Shards& src, size_t cols, uint8_t* raw, size_t span_cols,
+                     bool* repack) {
+    *repack = dense_span(src.nblocks, span_cols, src.dbs, src.ss, src.len);
     if (*repack) {
-        HIP_TRY(hipMemcpyAsync(raw, src, span_bytes(nb, span_cols, bs, ss, len), hipMemcpyHostToDevice, up));
+        const size_t span = span_bytes(src.nblocks, span_cols, src.dbs, src.ss, src.len);
+        HIP_TRY(hipMemcpyAsync(raw, src.data, span, hipMemcpyHostToDevice, up));
         return FEC_OK;
     }
     for (size_t j = 0; j < cols; ++j)
-        HIP_TRY(hipMemcpy2DAsync(stage + j * st_ss, st_bs, src + j * ss, bs, len, nb, hipMemcpyHostToDevice, up));
+        HIP_TRY(hipMemcpy2DAsync(st.shard(0, j), st.dbs, src.shard(0, j), src.dbs, src.len, src.nblocks,
+                                 hipMemcpyHostToDevice, up));
     return FEC_OK;
 }
 
@@ -153,17 +155,17 @@ static int pinned_up(hipStream_t up, uint8_t* stage, size_t st_bs, size_t st_ss,
 // device stage into one image that goes down in one linear DMA.
 static bool packed_out(size_t bs, size_t ss, size_t cols, size_t len) { return ss == len && bs == cols * len; }
 
-// Device stage [nb][st_bs/st_ss] columns back to the caller, on stream `down`: the packed image
-// (packed_out) in one linear DMA, else one 2D DMA per column, which writes exactly len bytes per
-// shard.
-static int pinned_down(hipStream_t down, uint8_t* dst, size_t bs, size_t ss, const uint8_t* stage, size_t st_bs,
-                       size_t st_ss, size_t nb, size_t cols, size_t len, const uint8_t* raw) {
-    if (packed_out(bs, ss, cols, len)) {
-        HIP_TRY(hipMemcpyAsync(dst, raw, nb * cols * len, hipMemcpyDeviceToHost, down));
+// The parity columns [0, cols) of the device stage `st` back to the caller's blocks `dst`, on stream
+// `down`: the packed image (packed_out) in one linear DMA, else one 2D DMA per column, which writes
+// exactly len bytes per shard.
+static int pinned_down(hipStream_t down, const Shards& dst, const Shards& st, size_t cols, const uint8_t* raw) {
+    if (packed_out(dst.pbs, dst.pss, cols, dst.len)) {
+        HIP_TRY(hipMemcpyAsync(dst.parity, raw, dst.nblocks * cols * dst.len, hipMemcpyDeviceToHost, down));
         return FEC_OK;
     }
     for (size_t j = 0; j < cols; ++j)
-        HIP_TRY(hipMemcpy2DAsync(dst + j * ss, bs, stage + j * st_ss, st_bs, len, nb, hipMemcpyDeviceToHost, down));
+        HIP_TRY(hipMemcpy2DAsync(dst.par(0, j), dst.pbs, st.par(0, j), st.pbs, dst.len, dst.nblocks,
+                                 hipMemcpyDeviceToHost, down));
     return FEC_OK;
 }
 
@@ -283,62 +285,64 @@ static int host_pipeline(fec_ctx* ctx, size_t nblocks, size_t chunk, Up up, Kern
     return rc;
 }
 
-// Encode (RS when code != nullptr, else XOR(k, 1)): host data -> host parity.
-int host_encode(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nblocks, const uint8_t* data,
-                size_t dbs, uint8_t* parity, size_t pbs, size_t ss, bool pinned) {
-    const size_t ssd = round16(len);
-    const size_t chunk = host_chunk_blocks(nblocks, (size_t)k * ssd);
+// Encode (RS when code != nullptr, else XOR(k, 1)): host data -> host parity. A chunk is staged
+// block-major, its data as [nb][k][ssd] in the set's in buffers and its parity as [nb][m][ssd] in the
+// out buffers.
+int host_encode(fec_ctx* ctx, Code* code, int k, int m, const Shards& s, bool pinned) {
+    const size_t len = s.len, ssd = round16(len);
+    const size_t chunk = host_chunk_blocks(s.nblocks, (size_t)k * ssd);
     HostPipe& p = ctx->pipe;
     int rc;
     if ((rc = host_pipe_grow(p, chunk * k * ssd, chunk * m * ssd, 1))) return rc;
-    const bool pack = pinned && packed_out(pbs, ss, (size_t)m, len);
+    const bool pack = pinned && packed_out(s.pbs, s.pss, (size_t)m, len);
     if (pinned)
-        for (HostSet& s : p.set) {
-            if ((rc = grow_dev(&s.d_raw_in, &s.raw_in_cap, span_bytes(chunk, k, dbs, ss, len) + 16))) return rc;
-            if (pack && (rc = grow_dev(&s.d_raw_out, &s.raw_out_cap, chunk * m * len + 16))) return rc;
+        for (HostSet& hs : p.set) {
+            if ((rc = grow_dev(&hs.d_raw_in, &hs.raw_in_cap, span_bytes(chunk, k, s.dbs, s.ss, len) + 16))) return rc;
+            if (pack && (rc = grow_dev(&hs.d_raw_out, &hs.raw_out_cap, chunk * m * len + 16))) return rc;
         }
-    auto up = [&](HostSet& s, HostChunk& ch) -> int {
-        if (pinned)
-            return pinned_up(p.up, s.d_in, (size_t)k * ssd, ssd, data + ch.b0 * dbs, dbs, ss, ch.nb, k, len, s.d_raw_in,
-                             k, &ch.repack);
+    auto staged = [&](uint8_t* in, uint8_t* out, size_t nb) -> Shards {
+        return {len, nb, in, (size_t)k * ssd, out, (size_t)m * ssd, ssd, ssd};
+    };
+    auto up = [&](HostSet& hs, HostChunk& ch) -> int {
+        const Shards src = s.blocks(ch.b0, ch.nb);
+        if (pinned) return pinned_up(p.up, staged(hs.d_in, hs.d_out, ch.nb), src, k, hs.d_raw_in, k, &ch.repack);
+        const Shards h = staged(hs.h_in, hs.h_out, ch.nb);
         parallel_for(ch.nb, [&](size_t lo, size_t hi) {
             for (size_t b = lo; b < hi; ++b)
-                for (int j = 0; j < k; ++j) memcpy(s.h_in + (b * k + j) * ssd, data + (ch.b0 + b) * dbs + j * ss, len);
+                for (int j = 0; j < k; ++j) memcpy(h.shard(b, j), src.shard(b, j), len);
         });
-        HIP_TRY(hipMemcpyAsync(s.d_in, s.h_in, ch.nb * k * ssd, hipMemcpyHostToDevice, p.up));
+        HIP_TRY(hipMemcpyAsync(hs.d_in, hs.h_in, ch.nb * k * ssd, hipMemcpyHostToDevice, p.up));
         return FEC_OK;
     };
-    auto kern = [&](HostSet& s, HostChunk& ch) -> int {
+    auto kern = [&](HostSet& hs, HostChunk& ch) -> int {
+        const Shards st = staged(hs.d_in, hs.d_out, ch.nb);
         if (ch.repack)
-            HIP_TRY(fk::launch_span_to_stage(s.d_in, (size_t)k * ssd, ssd, s.d_raw_in, dbs, ss, (uint32_t)ch.nb,
+            HIP_TRY(fk::launch_span_to_stage(st.data, st.dbs, st.ss, hs.d_raw_in, s.dbs, s.ss, (uint32_t)ch.nb,
                                              (uint32_t)k, (uint32_t)len, p.comp));
-        const int r = on_pipe(ctx, [&] {
-            return code ? rs_encode_device(ctx, code, len, ch.nb, s.d_in, (size_t)k * ssd, s.d_out, (size_t)m * ssd, ssd)
-                        : xor_encode_device(ctx, k, len, ch.nb, s.d_in, (size_t)k * ssd, s.d_out, ssd, ssd);
-        });
+        const int r =
+            on_pipe(ctx, [&] { return code ? rs_encode_device(ctx, code, st) : xor_encode_device(ctx, k, st); });
         if (r) return r;
         if (pack)
-            HIP_TRY(fk::launch_stage_to_packed(s.d_raw_out, s.d_out, (size_t)m * ssd, ssd, (uint32_t)ch.nb,
-                                               (uint32_t)m, (uint32_t)len, p.comp));
+            HIP_TRY(fk::launch_stage_to_packed(hs.d_raw_out, st.parity, st.pbs, st.pss, (uint32_t)ch.nb, (uint32_t)m,
+                                               (uint32_t)len, p.comp));
         return FEC_OK;
     };
-    auto down = [&](HostSet& s, HostChunk& ch) -> int {
+    auto down = [&](HostSet& hs, HostChunk& ch) -> int {
         if (pinned)
-            return pinned_down(p.down, parity + ch.b0 * pbs, pbs, ss, s.d_out, (size_t)m * ssd, ssd, ch.nb, m, len,
-                               s.d_raw_out);
-        HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, ch.nb * m * ssd, hipMemcpyDeviceToHost, p.down));
+            return pinned_down(p.down, s.blocks(ch.b0, ch.nb), staged(hs.d_in, hs.d_out, ch.nb), m, hs.d_raw_out);
+        HIP_TRY(hipMemcpyAsync(hs.h_out, hs.d_out, ch.nb * m * ssd, hipMemcpyDeviceToHost, p.down));
         return FEC_OK;
     };
-    auto finish = [&](HostSet& s, HostChunk& ch) -> int {
-        if (!pinned)
-            parallel_for(ch.nb, [&](size_t lo, size_t hi) {
-                for (size_t b = lo; b < hi; ++b)
-                    for (int r = 0; r < m; ++r)
-                        memcpy(parity + (ch.b0 + b) * pbs + r * ss, s.h_out + (b * m + r) * ssd, len);
-            });
+    auto finish = [&](HostSet& hs, HostChunk& ch) -> int {
+        if (pinned) return FEC_OK;
+        const Shards dst = s.blocks(ch.b0, ch.nb), h = staged(hs.h_in, hs.h_out, ch.nb);
+        parallel_for(ch.nb, [&](size_t lo, size_t hi) {
+            for (size_t b = lo; b < hi; ++b)
+                for (int r = 0; r < m; ++r) memcpy(dst.par(b, r), h.par(b, r), len);
+        });
         return FEC_OK;
     };
-    return host_pipeline(ctx, nblocks, chunk, up, kern, down, finish);
+    return host_pipeline(ctx, s.nblocks, chunk, up, kern, down, finish);
 }
 
 // RS reconstruct, in place in the caller's data slots: per chunk, the data shards and the parity
@@ -351,31 +355,37 @@ int host_encode(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nbloc
 // straight from the caller's buffer (gather_planes_kernel), which moves only what is read but runs
 // slower beside a D2H copy (pcie_duplex_probe: a kernel reading host memory and a D2H DMA at once
 // make 29.9 GB/s each way).
-int host_reconstruct_rs(fec_ctx* ctx, Code* code, int k, int m, size_t len, size_t nblocks, uint8_t* data,
-                        size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                        int32_t* block_status, bool pinned) {
-    const size_t ssd = round16(len);
+int host_reconstruct_rs(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* masks, int32_t* block_status,
+                        bool pinned) {
+    const int k = code->k, m = code->m;
+    const size_t len = s.len, ssd = round16(len);
     const size_t n = (size_t)k + m;
     const uint32_t all = fk::low_mask((uint32_t)n), kmask = fk::low_mask((uint32_t)k);
     const size_t maxe = (size_t)std::max(1, std::min(k, m));
-    const size_t chunk = host_chunk_blocks(nblocks, n * ssd);
+    const size_t chunk = host_chunk_blocks(s.nblocks, n * ssd);
     HostPipe& p = ctx->pipe;
     int rc;
     if ((rc = host_pipe_grow(p, chunk * n * ssd, chunk * maxe * ssd, chunk))) return rc;
     if (pinned)
-        for (HostSet& s : p.set)
-            if ((rc = grow_dev(&s.d_raw_in, &s.raw_in_cap, span_bytes(chunk, k, dbs, ss, len) + 16))) return rc;
+        for (HostSet& hs : p.set)
+            if ((rc = grow_dev(&hs.d_raw_in, &hs.raw_in_cap, span_bytes(chunk, k, s.dbs, s.ss, len) + 16))) return rc;
     // the sticky device word of the host path: statuses report every per-block failure, but a plan
     // kernel that cannot run (fec_plan.hip form 3's LDS-alignment guard, bit 4) writes no statuses
     HIP_TRY(hipMemsetAsync(ctx->d_err + 1, 0, sizeof(int), p.comp));
     bool failed = false;
-    auto up = [&](HostSet& s, HostChunk& ch) -> int {
-        const size_t nb = ch.nb, b0 = ch.b0;
+    // A chunk's stage in a set's in buffer at `in`: the data block-major, [nb][k][ssd], then the parity
+    // plane-major, [P][nb][ssd], so that only the planes a chunk reads cross PCIe.
+    auto staged = [&](uint8_t* in, size_t nb) -> Shards {
+        return {len, nb, in, (size_t)k * ssd, in + nb * k * ssd, /*pbs*/ ssd, /*ss*/ ssd, /*pss*/ nb * ssd};
+    };
+    auto up = [&](HostSet& hs, HostChunk& ch) -> int {
+        const size_t nb = ch.nb;
+        const Shards src = s.blocks(ch.b0, nb), st = staged(hs.d_in, nb);
         // per block: the parity planes its first k present shards reach, its erasure count
         uint32_t needers[32] = {};
         for (size_t b = 0; b < nb; ++b) {
-            const uint32_t mask = masks[b0 + b] & all;
-            s.h_masks[b] = mask;
+            const uint32_t mask = masks[ch.b0 + b] & all;
+            hs.h_masks[b] = mask;
             const uint32_t e = (uint32_t)k - (uint32_t)__builtin_popcount(mask & kmask);
             if (e == 0 || (uint32_t)__builtin_popcount(mask) < (uint32_t)k) continue;
             uint32_t need = e;   // parities among the first k present: the first e present ones
@@ -387,18 +397,13 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, int k, int m, size_t len, size
                 }
             ch.slots = std::max(ch.slots, (size_t)e);
         }
-        uint8_t* d_par = s.d_in + nb * k * ssd;   // parity planes [P][nb][ssd]
-        HIP_TRY(hipMemcpyAsync(s.d_masks, s.h_masks, nb * 4, hipMemcpyHostToDevice, p.up));
+        HIP_TRY(hipMemcpyAsync(hs.d_masks, hs.h_masks, nb * 4, hipMemcpyHostToDevice, p.up));
         if (pinned) {
-            if ((rc = pinned_up(p.up, s.d_in, (size_t)k * ssd, ssd, data + b0 * dbs, dbs, ss, nb, k, len, s.d_raw_in, k,
-                                &ch.repack)))
-                return rc;
+            if ((rc = pinned_up(p.up, st, src, k, hs.d_raw_in, k, &ch.repack))) return rc;
             // the device reads sparse planes straight out of the caller's pinned buffer (needs a
             // device mapping of it; otherwise every plane goes by DMA)
             const uint8_t* dpar = nullptr;
-            const bool mapped = ch.planes &&
-                                hipHostGetDevicePointer((void**)&dpar, (void*)(parity + b0 * pbs), 0) == hipSuccess &&
-                                dpar;
+            const bool mapped = ch.planes && hipHostGetDevicePointer((void**)&dpar, src.parity, 0) == hipSuccess && dpar;
             if (ch.planes && !mapped) (void)hipGetLastError();
             for (size_t r = 0; r < ch.planes; ++r) {
                 const bool sparse = needers[r] * 4 < nb * 3;
@@ -406,67 +411,67 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, int k, int m, size_t len, size
                     ch.gather |= 1u << r;
                     continue;
                 }
-                HIP_TRY(hipMemcpy2DAsync(d_par + r * nb * ssd, ssd, parity + b0 * pbs + r * ss, pbs, len, nb,
-                                         hipMemcpyHostToDevice, p.up));
+                HIP_TRY(hipMemcpy2DAsync(st.par(0, r), st.pbs, src.par(0, r), src.pbs, len, nb, hipMemcpyHostToDevice,
+                                         p.up));
             }
             return FEC_OK;
         }
         const size_t P = ch.planes;
+        const Shards h = staged(hs.h_in, nb);
         parallel_for(nb, [&](size_t lo, size_t hi) {
             for (size_t b = lo; b < hi; ++b) {
-                const uint32_t mask = s.h_masks[b];
+                const uint32_t mask = hs.h_masks[b];
                 if ((mask & kmask) == kmask) continue;   // nothing to rebuild: nothing read
                 for (int j = 0; j < k; ++j)
-                    if ((mask >> j) & 1u) memcpy(s.h_in + (b * k + j) * ssd, data + (b0 + b) * dbs + j * ss, len);
+                    if ((mask >> j) & 1u) memcpy(h.shard(b, j), src.shard(b, j), len);
                 for (size_t r = 0; r < P; ++r)
-                    if ((mask >> (k + r)) & 1u)
-                        memcpy(s.h_in + nb * k * ssd + (r * nb + b) * ssd, parity + (b0 + b) * pbs + r * ss, len);
+                    if ((mask >> (k + r)) & 1u) memcpy(h.par(b, r), src.par(b, r), len);
             }
         });
-        HIP_TRY(hipMemcpyAsync(s.d_in, s.h_in, (nb * k + P * nb) * ssd, hipMemcpyHostToDevice, p.up));
+        HIP_TRY(hipMemcpyAsync(hs.d_in, hs.h_in, (nb * k + P * nb) * ssd, hipMemcpyHostToDevice, p.up));
         return FEC_OK;
     };
-    auto kern = [&](HostSet& s, HostChunk& ch) -> int {
+    auto kern = [&](HostSet& hs, HostChunk& ch) -> int {
         const size_t nb = ch.nb;
-        uint8_t* d_par = s.d_in + nb * k * ssd;
+        const Shards st = staged(hs.d_in, nb);
         if (ch.repack)
-            HIP_TRY(fk::launch_span_to_stage(s.d_in, (size_t)k * ssd, ssd, s.d_raw_in, dbs, ss, (uint32_t)nb,
-                                             (uint32_t)k, (uint32_t)len, p.comp));
+            HIP_TRY(fk::launch_span_to_stage(st.data, st.dbs, st.ss, hs.d_raw_in, s.dbs, s.ss, (uint32_t)nb, (uint32_t)k,
+                                             (uint32_t)len, p.comp));
         if (ch.gather) {
             const uint8_t* dpar = nullptr;
-            HIP_TRY(hipHostGetDevicePointer((void**)&dpar, (void*)(parity + ch.b0 * pbs), 0));
-            HIP_TRY(fk::launch_gather_planes(dpar, pbs, ss, (uint32_t)len, s.d_masks, (uint32_t)nb, (uint32_t)ch.planes,
-                                             ch.gather, (uint32_t)k, d_par, ssd, p.comp));
+            HIP_TRY(hipHostGetDevicePointer((void**)&dpar, s.blocks(ch.b0, nb).parity, 0));
+            HIP_TRY(fk::launch_gather_planes(dpar, s.pbs, s.pss, (uint32_t)len, hs.d_masks, (uint32_t)nb,
+                                             (uint32_t)ch.planes, ch.gather, (uint32_t)k, st.parity, st.pbs, p.comp));
         }
         return on_pipe(ctx, [&] {
-            return rs_reconstruct_device(ctx, code, len, nb, s.d_in, (size_t)k * ssd, d_par, ssd, ssd, s.d_masks,
-                                         s.d_status, ctx->d_err + 1, s.d_out, ch.slots * ssd, (uint32_t)ch.slots,
-                                         nb * ssd);
+            return rs_reconstruct_device(ctx, code,
+                                         {st, {hs.d_masks, 1, hs.d_status, ctx->d_err + 1},
+                                          {hs.d_out, ch.slots * ssd, (uint32_t)ch.slots}});
         });
     };
-    auto down = [&](HostSet& s, HostChunk& ch) -> int {
-        HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, ch.nb * ch.slots * ssd, hipMemcpyDeviceToHost, p.down));
-        HIP_TRY(hipMemcpyAsync(s.h_status, s.d_status, ch.nb * 4, hipMemcpyDeviceToHost, p.down));
+    auto down = [&](HostSet& hs, HostChunk& ch) -> int {
+        HIP_TRY(hipMemcpyAsync(hs.h_out, hs.d_out, ch.nb * ch.slots * ssd, hipMemcpyDeviceToHost, p.down));
+        HIP_TRY(hipMemcpyAsync(hs.h_status, hs.d_status, ch.nb * 4, hipMemcpyDeviceToHost, p.down));
         return FEC_OK;
     };
-    auto finish = [&](HostSet& s, HostChunk& ch) -> int {
+    auto finish = [&](HostSet& hs, HostChunk& ch) -> int {
         for (size_t b = 0; b < ch.nb; ++b) {
-            const int32_t st = s.h_status[b];
+            const int32_t st = hs.h_status[b];
             if (block_status) block_status[ch.b0 + b] = st < 0 ? st : 0;
             if (st < 0) failed = true;
         }
+        const Shards dst = s.blocks(ch.b0, ch.nb);
         parallel_for(ch.nb, [&](size_t lo, size_t hi) {
             for (size_t b = lo; b < hi; ++b) {
-                const int32_t st = s.h_status[b];
-                const uint32_t mask = s.h_masks[b];
+                const int32_t st = hs.h_status[b];
+                const uint32_t mask = hs.h_masks[b];
                 for (int j = 0, r = 0; j < k && r < st; ++j)
-                    if (!((mask >> j) & 1u))
-                        memcpy(data + (ch.b0 + b) * dbs + j * ss, s.h_out + (b * ch.slots + r++) * ssd, len);
+                    if (!((mask >> j) & 1u)) memcpy(dst.shard(b, j), hs.h_out + (b * ch.slots + r++) * ssd, len);
             }
         });
         return FEC_OK;
     };
-    if ((rc = host_pipeline(ctx, nblocks, chunk, up, kern, down, finish))) return rc;
+    if ((rc = host_pipeline(ctx, s.nblocks, chunk, up, kern, down, finish))) return rc;
     int err = 0;
     HIP_TRY(hipMemcpyAsync(&err, ctx->d_err + 1, sizeof(int), hipMemcpyDeviceToHost, p.comp));
     HIP_TRY(hipStreamSynchronize(p.comp));
@@ -479,38 +484,42 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, int k, int m, size_t len, size
 // Present masks of mask_words words per block, bits at and above n ignored. Each chunk of blocks
 // goes as [block][n][ssd] through the ctx's pinned and device stage (a block with every data shard
 // present is not staged: the kernels load a block's shards only to rebuild one of them), is rebuilt
-// in place on the device by core(nb, stage, block stride, ssd, masks, statuses), and the rebuilt
+// in place on the device by core(the device stage's layout, its masks and statuses), and the rebuilt
 // data shards of the blocks that succeeded are copied back. A block fails exactly when its status is
 // not 0 (fec_xor.hip and fec_wide.hip set the sticky word d_err[1] with such a status, never
 // without).
 template <class Core>
-static int host_reconstruct_plain(fec_ctx* ctx, size_t k, size_t n, size_t len, size_t nblocks, uint8_t* data,
-                                  size_t dbs, const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
+static int host_reconstruct_plain(fec_ctx* ctx, size_t k, size_t n, const Shards& s, const uint32_t* masks,
                                   size_t mask_words, int32_t* block_status, Core core) {
-    const size_t ssd = round16(len);
-    const size_t chunk = host_chunk_blocks(nblocks, n * ssd);
+    const size_t len = s.len, ssd = round16(len);
+    const size_t chunk = host_chunk_blocks(s.nblocks, n * ssd);
     int rc;
     if ((rc = grow_stage(ctx, chunk * n * ssd))) return rc;
     if ((rc = grow_masks(ctx, chunk * mask_words))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_err + 1, 0, sizeof(int), ctx->stream));   // (the kernels OR into it)
     auto present = [&](size_t b, size_t i) { return (masks[b * mask_words + i / 32] >> (i % 32)) & 1u; };
+    auto staged = [&](uint8_t* base, size_t nb) -> Shards {
+        return {len, nb, base, n * ssd, base + k * ssd, n * ssd, ssd, ssd};
+    };
+    // shard i of the n of block b: data shard i, or parity shard i - k
+    auto shard = [&](const Shards& x, size_t b, size_t i) { return i < k ? x.shard(b, i) : x.par(b, i - k); };
     std::vector<int32_t> st;
     bool failed = false;
-    for (size_t b0 = 0; b0 < nblocks; b0 += chunk) {
-        const size_t nb = std::min(chunk, nblocks - b0);
+    for (size_t b0 = 0; b0 < s.nblocks; b0 += chunk) {
+        const size_t nb = std::min(chunk, s.nblocks - b0);
+        const Shards src = s.blocks(b0, nb), h = staged(ctx->h_stage, nb);
         for (size_t b = 0; b < nb; ++b) {
             size_t have = 0;
             while (have < k && present(b0 + b, have)) ++have;
             if (have == k) continue;   // nothing to rebuild: nothing read
             for (size_t i = 0; i < n; ++i)
-                if (present(b0 + b, i))
-                    memcpy(ctx->h_stage + (b * n + i) * ssd,
-                           i < k ? data + (b0 + b) * dbs + i * ss : parity + (b0 + b) * pbs + (i - k) * ss, len);
+                if (present(b0 + b, i)) memcpy(shard(h, b, i), shard(src, b, i), len);
         }
         HIP_TRY(hipMemcpyAsync(ctx->d_masks, masks + b0 * mask_words, nb * mask_words * 4, hipMemcpyHostToDevice,
                                ctx->stream));
         HIP_TRY(hipMemcpyAsync(ctx->d_stage, ctx->h_stage, nb * n * ssd, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = core(nb, ctx->d_stage, n * ssd, ssd, ctx->d_masks, ctx->d_status))) return rc;
+        if ((rc = core(staged(ctx->d_stage, nb), DecodeWords{ctx->d_masks, mask_words, ctx->d_status, ctx->d_err + 1})))
+            return rc;
         st.resize(nb);
         HIP_TRY(hipMemcpyAsync(st.data(), ctx->d_status, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipMemcpyAsync(ctx->h_stage, ctx->d_stage, nb * n * ssd, hipMemcpyDeviceToHost, ctx->stream));
@@ -522,32 +531,25 @@ static int host_reconstruct_plain(fec_ctx* ctx, size_t k, size_t n, size_t len, 
                 continue;
             }
             for (size_t i = 0; i < k; ++i)
-                if (!present(b0 + b, i)) memcpy(data + (b0 + b) * dbs + i * ss, ctx->h_stage + (b * n + i) * ssd, len);
+                if (!present(b0 + b, i)) memcpy(src.shard(b, i), h.shard(b, i), len);
         }
     }
     return failed ? FEC_ERR_TOO_FEW_SHARDS : FEC_OK;
 }
 
-int host_reconstruct_xor(fec_ctx* ctx, int k, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                         const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks,
-                         int32_t* block_status) {
-    return host_reconstruct_plain(
-        ctx, k, (size_t)k + 1, len, nblocks, data, dbs, parity, pbs, ss, masks, 1, block_status,
-        [&](size_t nb, uint8_t* stage, size_t bs, size_t ssd, const uint32_t* d_masks, int32_t* d_status) {
-            return xor_reconstruct_device(ctx, k, len, nb, stage, bs, stage + k * ssd, bs, ssd, d_masks, d_status,
-                                          ctx->d_err + 1);
-        });
+int host_reconstruct_xor(fec_ctx* ctx, int k, const Shards& s, const uint32_t* masks, int32_t* block_status) {
+    return host_reconstruct_plain(ctx, k, (size_t)k + 1, s, masks, 1, block_status,
+                                  [&](const Shards& st, const DecodeWords& w) {
+                                      return xor_reconstruct_device(ctx, k, st, w);
+                                  });
 }
 
-int host_reconstruct_wide(fec_ctx* ctx, int k, int m, size_t len, size_t nblocks, uint8_t* data, size_t dbs,
-                          const uint8_t* parity, size_t pbs, size_t ss, const uint32_t* masks, size_t mask_words,
+int host_reconstruct_wide(fec_ctx* ctx, int k, int m, const Shards& s, const uint32_t* masks, size_t mask_words,
                           int32_t* block_status) {
-    return host_reconstruct_plain(
-        ctx, k, (size_t)k + m, len, nblocks, data, dbs, parity, pbs, ss, masks, mask_words, block_status,
-        [&](size_t nb, uint8_t* stage, size_t bs, size_t ssd, const uint32_t* d_masks, int32_t* d_status) {
-            return rs_reconstruct_wide_device(ctx, k, m, len, nb, stage, bs, stage + k * ssd, bs, ssd, d_masks,
-                                              mask_words, d_status, ctx->d_err + 1);
-        });
+    return host_reconstruct_plain(ctx, k, (size_t)k + m, s, masks, mask_words, block_status,
+                                  [&](const Shards& st, const DecodeWords& w) {
+                                      return rs_reconstruct_wide_device(ctx, k, m, {st, w, {}});
+                                  });
 }
 
 extern "C" {

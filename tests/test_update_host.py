@@ -3,7 +3,8 @@ are declared with the right constness and exported, each has a row in the header
 Codec methods exist, the argument checks that return before any device work come in the uniform
 calls' order with the mask_words bound following k (not k + m), and the per-launch argument fill of
 a batch that the launch limit cuts (fec__selftest_update_slices) gives every launch the bases, mask
-pointer, item count, row count and table base that the call's strides imply."""
+pointer, item count, row count and table base that the call's strides imply; and the slicing of a
+batch that every call's launches share (fec__selftest_batch_slices)."""
 import ctypes
 import os
 import re
@@ -108,3 +109,10 @@ def test_launch_arguments_of_a_cut_batch(fec):
     # region bases, mask pointer, total, m and table base of each against the call's strides
     lib = ctypes.CDLL(fec._LIB_PATH)
     assert lib.fec__selftest_update_slices() == 0
+
+
+def test_a_slice_of_a_batch_moves_each_base_by_its_own_stride(fec):
+    # the one function every core and host chunk slices with: data, parity, out, mask and status bases
+    # of blocks [b0, b0 + nb) of a layout whose strides all differ; nothing else moves
+    lib = ctypes.CDLL(fec._LIB_PATH)
+    assert lib.fec__selftest_batch_slices() == 0
