@@ -28,10 +28,11 @@ RS_CASES = [(2, 1, 1202), (6, 2, 1202), (8, 4, 1202), (16, 8, 1202), (20, 10, 12
 STEPS = ["encode", "reconstruct", "recover_m", "recover_1"]
 
 
-def make_layout(name, k, m, L, slots):
-    """(arena, data region, parity region, out arena, out region) for one layout; every offset and
-    stride a multiple of 16, at least GUARD canary bytes before the first and after the last slot.
-    The out region of a recover lies in an arena of its own, shard-major where the inputs are."""
+def make_layout(name, k, m, L, slots, B=B):
+    """(arena, data region, parity region, out arena, out region) for one layout of B blocks; every
+    offset and stride a multiple of 16, at least GUARD canary bytes before the first and after the
+    last slot. The out region of a recover lies in an arena of its own, shard-major where the inputs
+    are."""
     data, par = place(name, k, m, L, B)
     if name.startswith("shard_major"):
         out = Region(GUARD, data.bs, data.ss, slots, B)
@@ -40,9 +41,10 @@ def make_layout(name, k, m, L, slots):
     return canary_image([data, par]), data, par, canary_image([out]), out
 
 
-def make_masks(rng, k, m):
+def make_masks(rng, k, m, B=B):
     """Present masks of B blocks over five kinds, every kind the code can have present: intact,
-    parity-only loss, one data shard lost, 2..min(k, m) data shards lost, too few shards."""
+    parity-only loss, one data shard lost, 2..min(k, m) data shards lost, too few shards. The kinds
+    are dealt in turn and then shuffled, so a batch of as many blocks as kinds holds one of each."""
     n = k + m
     kinds = [0, 1, 2, 4] + ([3] if min(k, m) >= 2 else [])
     kind = np.array((kinds * (B // len(kinds) + 1))[:B])
@@ -77,19 +79,25 @@ def classify(masks, k, m):
 _cases = {}
 
 
-def rs_case(oracle, k, m, L):
-    """Host side of one (k, m, L) case, computed once: shards [B, n, L] with the oracle's parity,
-    masks of all five kinds, and the oracle's in-place reconstruct of the damaged batch."""
-    key = (k, m, L)
+def rs_case(oracle, k, m, L, B=B, single_only=False):
+    """Host side of one (k, m, L, B) case, computed once: shards [B, n, L] with the oracle's parity,
+    masks of all five kinds, and the oracle's in-place reconstruct of the damaged batch. single_only:
+    the blocks of the fourth kind lose one data shard too, so no recoverable block loses two."""
+    key = (k, m, L, B, single_only)
     if key not in _cases:
         n = k + m
         rng = np.random.default_rng(100000 * k + 1000 * m + L)
         sh = np.zeros((B, n, L), dtype=np.uint8)
         sh[:, :k] = rng.integers(0, 256, (B, k, L), dtype=np.uint8)
         oracle.rs_encode(k, m, sh)
-        masks = make_masks(rng, k, m)
+        masks = make_masks(rng, k, m, B)
+        if single_only:
+            lost, e_d, few, kind = classify(masks, k, m)
+            for b in np.flatnonzero(kind == 3):   # all its lost data shards but the lowest are present again
+                extra = np.flatnonzero(lost[b, :k])[1:]
+                masks[b] |= np.uint32(sum(1 << int(i) for i in extra))
         lost, e_d, few, kind = classify(masks, k, m)
-        want_kinds = {0, 1, 2, 4} | ({3} if min(k, m) >= 2 else set())
+        want_kinds = {0, 1, 2, 4} | ({3} if min(k, m) >= 2 and not single_only else set())
         assert set(kind.tolist()) == want_kinds, "every block kind the code can have must be present"
         if 3 in want_kinds:
             assert (e_d[kind == 3] >= 2).all() and e_d[~few].max() <= min(k, m)
@@ -110,11 +118,10 @@ def rs_case(oracle, k, m, L):
 def fill_damaged(arena, data, par, c, k, L):
     """The encoded batch with its erased shards overwritten (bytes [0, round_up(L, 16)))."""
     R = rup16(L)
-    arena[data.index(0, L)] = c["dmg"][:, :k]
-    arena[par.index(0, L)] = c["dmg"][:, k:]
+    data.view(arena, 0, L)[...] = c["dmg"][:, :k]
+    par.view(arena, 0, L)[...] = c["dmg"][:, k:]
     for reg, lost in ((data, c["lost"][:, :k]), (par, c["lost"][:, k:])):
-        pad = reg.index(L, R)
-        arena[pad[lost]] = ERASED
+        reg.view(arena, L, R)[lost] = ERASED
 
 
 def expect_sync(codec, fec, st_want):
@@ -126,17 +133,20 @@ def expect_sync(codec, fec, st_want):
 
 
 def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
-    """One call on one layout; checks the whole arena(s), the statuses and the sticky code."""
+    """One call on one layout; checks the whole arena(s), the statuses and the sticky code. The batch
+    is as many blocks as the case c holds. (The slots are reached through strided views of the
+    arenas, not index arrays: those would take eight bytes per shard byte.)"""
     R = rup16(L)
+    B = len(c["masks"])
     slots = 1 if step == "recover_1" else m
-    arena, data, par, oarena, out = make_layout(layout, k, m, L, slots)
+    arena, data, par, oarena, out = make_layout(layout, k, m, L, slots, B)
     masks = c["masks"] if masks is None else masks
     h = codec.handle
     if step == "encode":
-        arena[data.index(0, L)] = c["sh"][:, :k]
+        data.view(arena, 0, L)[...] = c["sh"][:, :k]
         model = arena.copy()
-        model[par.index(0, L)] = c["sh"][:, k:]
-        model[par.index(L, R)] = 0
+        par.view(model, 0, L)[...] = c["sh"][:, k:]
+        par.view(model, L, R)[...] = 0
         dev = torch.from_numpy(arena).cuda()
         p = dev.data_ptr()
         assert p % 16 == 0
@@ -156,8 +166,8 @@ def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
     lost_d, e_d, few = c["lost"][:, :k], c["e_d"], c["few"]
     if step == "reconstruct":
         rebuilt = lost_d & ~few[:, None]                       # erased data shards of recoverable blocks
-        model[data.index(0, L)[rebuilt]] = c["rec"][:, :k][rebuilt]
-        model[data.index(L, R)[rebuilt]] = 0
+        data.view(model, 0, L)[rebuilt] = c["rec"][:, :k][rebuilt]
+        data.view(model, L, R)[rebuilt] = 0
         st_want = np.where(few, fec.FEC_ERR_TOO_FEW_SHARDS, 0)
         rc = fec.lib.fec_rs_reconstruct_batch(h, k, m, L, B, p + data.off, data.bs, p + par.off, par.bs, data.ss,
                                               dm.data_ptr(), st.data_ptr(), fec.FEC_DEVICE)
@@ -194,30 +204,14 @@ def test_rs_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec,
     run_rs_step(codec, fec, torch, rs_case(oracle, k, m, L), layout, k, m, L, step)
 
 
-@pytest.mark.parametrize("L", [18, 1202])
-@pytest.mark.parametrize("layout", LAYOUTS)
-def test_xor_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec, layout, L):
-    """XOR(3,1) encode and in-place reconstruct (L = 18: masks by per-lane loads, L = 1202: by the
-    wave's scalar loads) on every layout, whole arena against the model."""
-    k, R = 3, rup16(L)
+def xor_case(oracle, rng, k, L, B=B):
+    """Host side of one XOR(k, 1) batch drawn from rng: shards [B, k + 1, L] with the oracle's parity,
+    masks over four kinds (intact, parity lost, one data shard lost, two shards lost with a data shard
+    among them), and the oracle's in-place reconstruct of the damaged batch."""
     n = k + 1
-    rng = np.random.default_rng(31 * L + LAYOUTS.index(layout))
     sh = np.zeros((B, n, L), dtype=np.uint8)
     sh[:, :k] = rng.integers(0, 256, (B, k, L), dtype=np.uint8)
     oracle.xor_encode(k, sh)
-    h = codec.handle
-    arena, data, par, _, _ = make_layout(layout, k, 1, L, 1)
-    arena[data.index(0, L)] = sh[:, :k]
-    model = arena.copy()
-    model[par.index(0, L)] = sh[:, k:]
-    model[par.index(L, R)] = 0
-    dev = torch.from_numpy(arena).cuda()
-    p = dev.data_ptr()
-    assert fec.lib.fec_xor_encode_batch(h, k, L, B, p + data.off, data.bs, p + par.off, par.bs, data.ss,
-                                        fec.FEC_DEVICE) == fec.FEC_OK
-    assert codec.lib_sync_rc() == fec.FEC_OK
-    check_arena(dev.cpu().numpy(), model, "xor encode")
-    # intact, parity lost, one data shard lost, two shards lost with a data shard among them
     kind = np.array(([0, 1, 2, 3] * B)[:B])
     rng.shuffle(kind)
     masks = np.empty(B, dtype=np.uint32)
@@ -234,13 +228,33 @@ def test_xor_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec
     st_ref = oracle.xor_reconstruct(k, rec, masks)
     fail = kind == 3
     assert np.array_equal(st_ref != 0, fail) and fail.any() and (kind == 2).any()
-    arena, data, par, _, _ = make_layout(layout, k, 1, L, 1)
-    fill_damaged(arena, data, par, dict(dmg=dmg, lost=lost), k, L)
-    model = arena.copy()
     rebuilt = lost[:, :k] & (kind == 2)[:, None]
     assert np.array_equal(rec[:, :k][rebuilt], sh[:, :k][rebuilt])
-    model[data.index(0, L)[rebuilt]] = rec[:, :k][rebuilt]
-    model[data.index(L, R)[rebuilt]] = 0
+    return dict(sh=sh, masks=masks, lost=lost, dmg=dmg, rec=rec, kind=kind, fail=fail, rebuilt=rebuilt)
+
+
+def run_xor(codec, fec, torch, c, layout, k, L):
+    """XOR(k, 1) encode and in-place reconstruct of the case c on one layout, whole arena against the
+    model, the statuses and the sticky code."""
+    R, B = rup16(L), len(c["masks"])
+    sh, masks, fail, rebuilt = c["sh"], c["masks"], c["fail"], c["rebuilt"]
+    h = codec.handle
+    arena, data, par, _, _ = make_layout(layout, k, 1, L, 1, B)
+    data.view(arena, 0, L)[...] = sh[:, :k]
+    model = arena.copy()
+    par.view(model, 0, L)[...] = sh[:, k:]
+    par.view(model, L, R)[...] = 0
+    dev = torch.from_numpy(arena).cuda()
+    p = dev.data_ptr()
+    assert fec.lib.fec_xor_encode_batch(h, k, L, B, p + data.off, data.bs, p + par.off, par.bs, data.ss,
+                                        fec.FEC_DEVICE) == fec.FEC_OK
+    assert codec.lib_sync_rc() == fec.FEC_OK
+    check_arena(dev.cpu().numpy(), model, "xor encode")
+    arena, data, par, _, _ = make_layout(layout, k, 1, L, 1, B)
+    fill_damaged(arena, data, par, c, k, L)
+    model = arena.copy()
+    data.view(model, 0, L)[rebuilt] = c["rec"][:, :k][rebuilt]
+    data.view(model, L, R)[rebuilt] = 0
     dev = torch.from_numpy(arena).cuda()
     p = dev.data_ptr()
     dm = torch.from_numpy(masks.view(np.int32).copy()).cuda()
@@ -251,6 +265,16 @@ def test_xor_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec
     expect_sync(codec, fec, st_want)
     assert np.array_equal(st.cpu().numpy(), st_want)
     check_arena(dev.cpu().numpy(), model, "xor reconstruct")
+
+
+@pytest.mark.parametrize("L", [18, 1202])
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_xor_layout_writes_only_what_the_header_allows(codec, oracle, torch, fec, layout, L):
+    """XOR(3,1) encode and in-place reconstruct (L = 18: masks by per-lane loads, L = 1202: by the
+    wave's scalar loads) on every layout, whole arena against the model."""
+    k = 3
+    rng = np.random.default_rng(31 * L + LAYOUTS.index(layout))
+    run_xor(codec, fec, torch, xor_case(oracle, rng, k, L), layout, k, L)
 
 
 @pytest.mark.parametrize("k,m", [(8, 4), (16, 8)])

@@ -22,7 +22,7 @@ from arena import codec, torch  # noqa: F401
 pytestmark = pytest.mark.gpu
 
 CASES = 400
-LENS = [1, 15, 16, 17, 200, 495, 496, 497, 512, 513, 1008, 1017, 1024, 1025, 1202, 1436]
+LENS = [1, 15, 16, 17, 200, 495, 496, 497, 512, 513, 1008, 1017, 1024, 1025, 1202, 1436, 4099]
 
 
 def _draw(rng):

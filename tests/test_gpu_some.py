@@ -29,7 +29,7 @@ def low_mask(n):
     return (1 << n) - 1
 
 
-def make_masks(rng, k, m):
+def make_masks(rng, k, m, B=B):
     """Present masks of B blocks cycling through the kinds the code can have: 0 intact, 1 parity-only
     loss, 2 one data shard, 3 mixed data and parity loss up to m, 4 exactly k present and all of them
     parity (m >= k), 5 k - 1 present."""
@@ -70,9 +70,9 @@ _cases = {}
 
 
 def make_case(oracle, k, m, L, masks, seed):
-    """Host side of one batch: shards [B, n, L] with the oracle's parity, the damaged batch, and the
-    oracle's full reconstruct of it (ReconstructData, then Encode on the result)."""
-    n = k + m
+    """Host side of one batch of len(masks) blocks: shards [B, n, L] with the oracle's parity, the
+    damaged batch, and the oracle's full reconstruct of it (ReconstructData, then Encode on the result)."""
+    n, B = k + m, len(masks)
     rng = np.random.default_rng(seed)
     sh = np.zeros((B, n, L), dtype=np.uint8)
     sh[:, :k] = rng.integers(0, 256, (B, k, L), dtype=np.uint8)
@@ -95,11 +95,11 @@ def make_case(oracle, k, m, L, masks, seed):
     return c
 
 
-def rs_case(oracle, k, m, L):
-    key = (k, m, L)
+def rs_case(oracle, k, m, L, B=B):
+    key = (k, m, L, B)
     if key not in _cases:
         rng = np.random.default_rng(100000 * k + 1000 * m + L)
-        masks, kind = make_masks(rng, k, m)
+        masks, kind = make_masks(rng, k, m, B)
         c = make_case(oracle, k, m, L, masks, 7 * L + k)
         nmiss = c["lost"].sum(axis=1)
         assert (~c["ok"]).any() and (nmiss[c["ok"]] == 0).any()
@@ -114,17 +114,18 @@ def rs_case(oracle, k, m, L):
 def fill_damaged(img, data, par, c, k, L):
     """The encoded batch with its erased shards overwritten (bytes [0, round_up(L, 16)))."""
     R = rup16(L)
-    img[data.index(0, L)] = c["dmg"][:, :k]
-    img[par.index(0, L)] = c["dmg"][:, k:]
+    data.view(img, 0, L)[...] = c["dmg"][:, :k]
+    par.view(img, 0, L)[...] = c["dmg"][:, k:]
     for reg, lost in ((data, c["lost"][:, :k]), (par, c["lost"][:, k:])):
-        img[reg.index(L, R)[lost]] = ERASED
+        reg.view(img, L, R)[lost] = ERASED
 
 
 def run_some(codec, fec, torch, c, layout, k, m, L, want=None, dev_masks=None, dev_want=None, mutate=None):
     """One call on one layout; checks the whole arena, the statuses and the sticky code against the
     model. want: uint32 [B] or None (every shard); dev_masks / dev_want: what the device is given
-    instead (stray bits). Returns (arena before the call, arena after, statuses, rebuilt [B, n])."""
-    n, R = k + m, rup16(L)
+    instead (stray bits). The batch is as many blocks as the case c holds; its slots are reached through
+    strided views of the arena. Returns (arena before the call, arena after, statuses, rebuilt [B, n])."""
+    n, R, B = k + m, rup16(L), len(c["masks"])
     data, par = place(layout, k, m, L, B)
     img = canary_image([data, par])
     fill_damaged(img, data, par, c, k, L)
@@ -136,8 +137,8 @@ def run_some(codec, fec, torch, c, layout, k, m, L, want=None, dev_masks=None, d
     rebuilt = rset & ~few[:, None]
     model = img.copy()
     for reg, rb, ref in ((data, rebuilt[:, :k], c["full"][:, :k]), (par, rebuilt[:, k:], c["full"][:, k:])):
-        model[reg.index(0, L)[rb]] = ref[rb]
-        model[reg.index(L, R)[rb]] = 0
+        reg.view(model, 0, L)[rb] = ref[rb]
+        reg.view(model, L, R)[rb] = 0
     dev = torch.from_numpy(img).cuda()
     p = dev.data_ptr()
     assert p % 16 == 0
@@ -212,11 +213,9 @@ def test_all_parity_lost_equals_encode(codec, oracle, torch, fec, k, m, L):
     check_arena(got, dev.cpu().numpy(), "reconstruct-some against fec_rs_encode_batch")
 
 
-@pytest.mark.parametrize("L", [33, 1202])
-@pytest.mark.parametrize("k,m", [(8, 4), (16, 8), (20, 10), (10, 22)])
-def test_want_mask_names_two_of_four_missing(codec, oracle, torch, fec, k, m, L):
-    """Every block misses two data and two parity shards; the want mask names one of each (and some
-    present shards): the other two missing slots keep 0x5A."""
+def two_of_four_case(oracle, k, m, L, B=B):
+    """(case, want masks): every block misses two data and two parity shards, and its want mask names
+    one of each and some present shards."""
     rng = np.random.default_rng(17 * k + L)
     masks = np.empty(B, dtype=np.uint32)
     want = np.empty(B, dtype=np.uint32)
@@ -225,7 +224,15 @@ def test_want_mask_names_two_of_four_missing(codec, oracle, torch, fec, k, m, L)
         q = k + rng.choice(m, size=2, replace=False)
         masks[b] = low_mask(k + m) & ~sum(1 << int(i) for i in list(d) + list(q))
         want[b] = (1 << int(d[1])) | (1 << int(q[0])) | (int(rng.integers(0, 1 << 32)) & int(masks[b]))
-    c = make_case(oracle, k, m, L, masks, 5 * L + k)
+    return make_case(oracle, k, m, L, masks, 5 * L + k), want
+
+
+@pytest.mark.parametrize("L", [33, 1202])
+@pytest.mark.parametrize("k,m", [(8, 4), (16, 8), (20, 10), (10, 22)])
+def test_want_mask_names_two_of_four_missing(codec, oracle, torch, fec, k, m, L):
+    """Every block misses two data and two parity shards; the want mask names one of each (and some
+    present shards): the other two missing slots keep 0x5A."""
+    c, want = two_of_four_case(oracle, k, m, L)
     _, got, st, rebuilt, _ = run_some(codec, fec, torch, c, "shard_major", k, m, L, want=want)
     assert (rebuilt.sum(axis=1) == 2).all() and (rebuilt[:, :k].sum(axis=1) == 1).all() and (st == 0).all()
 

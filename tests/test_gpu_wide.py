@@ -282,39 +282,59 @@ ARENA_B = 67
 
 
 class Slots:
-    """Shard slots at off + b*bs + r*ss of an arena."""
+    """Shard slots at off + b*bs + r*ss of an arena, b < B."""
 
-    def __init__(self, off, bs, ss, rows):
+    def __init__(self, off, bs, ss, rows, B=ARENA_B):
         assert off % 16 == 0 and bs % 16 == 0 and ss % 16 == 0
-        self.off, self.bs, self.ss, self.rows = off, bs, ss, rows
+        self.off, self.bs, self.ss, self.rows, self.B = off, bs, ss, rows, B
 
     def idx(self, lo, hi):
         """[B, rows, hi - lo] arena indices of bytes [lo, hi) of every slot."""
-        return (self.off + np.arange(ARENA_B)[:, None, None] * self.bs + np.arange(self.rows)[None, :, None] * self.ss
+        return (self.off + np.arange(self.B)[:, None, None] * self.bs + np.arange(self.rows)[None, :, None] * self.ss
                 + np.arange(lo, hi)[None, None, :])
 
     def end(self):
-        return self.off + (ARENA_B - 1) * self.bs + (self.rows - 1) * self.ss + self.ss
+        return self.off + (self.B - 1) * self.bs + (self.rows - 1) * self.ss + self.ss
 
 
-def arena_layout(name, k, m, L, slots):
+def arena_layout(name, k, m, L, slots, B=ARENA_B):
     R, n = rup16(L), k + m
     if name == "interleaved_slack":
         ss = R + 32
         bs = n * ss + 48
-        data, par = Slots(GUARD, bs, ss, k), Slots(GUARD + k * ss, bs, ss, m)
-        out = Slots(GUARD, slots * ss + 32, ss, slots)
+        data, par = Slots(GUARD, bs, ss, k, B), Slots(GUARD + k * ss, bs, ss, m, B)
+        out = Slots(GUARD, slots * ss + 32, ss, slots, B)
     elif name == "split_parity_below":
         ss = R + 16
-        par = Slots(GUARD, m * ss + 16, ss, m)
-        data = Slots(par.end() + 80, k * ss + 48, ss, k)
-        out = Slots(GUARD, slots * ss + 32, ss, slots)
+        par = Slots(GUARD, m * ss + 16, ss, m, B)
+        data = Slots(par.end() + 80, k * ss + 48, ss, k, B)
+        out = Slots(GUARD, slots * ss + 32, ss, slots, B)
     else:   # shard_major: [k + m][B][sp]
         sp = R + 16
-        ss = ARENA_B * sp
-        data, par = Slots(GUARD, sp, ss, k), Slots(GUARD + k * ss, sp, ss, m)
-        out = Slots(GUARD, sp, ss, slots)
+        ss = B * sp
+        data, par = Slots(GUARD, sp, ss, k, B), Slots(GUARD + k * ss, sp, ss, m, B)
+        out = Slots(GUARD, sp, ss, slots, B)
     return data, par, out
+
+
+ARENA_KINDS = [0, 1, 2, 7, 20, -1, 16, 17]   # data shards a block of RS(40,20) loses (-1: k - 1 shards present)
+
+
+def arena_case(oracle, layout, L, B=ARENA_B):
+    """(kinds, present, shards) of the RS(40,20) batch of the whole-arena test: the kinds dealt in turn
+    and shuffled, so a batch of eight blocks or more holds every one."""
+    k, m = 40, 20
+    n = k + m
+    rng = np.random.default_rng(L + len(layout))
+    kinds = np.array((ARENA_KINDS * 9)[:B])
+    rng.shuffle(kinds)
+    present = np.ones((B, n), dtype=bool)
+    for b in range(B):
+        if kinds[b] >= 0:
+            present[b] = erase_block(rng, k, m, int(kinds[b]))
+        else:
+            present[b, pick(rng, range(n), m + 1, [int(rng.integers(0, k))])] = False
+    return kinds, present, encoded(oracle, rng, B, k, m, L)
 
 
 @pytest.mark.parametrize("layout", ["interleaved_slack", "split_parity_below", "shard_major"])
@@ -323,19 +343,14 @@ def test_wide_calls_write_only_their_output_bytes(fec, codec, oracle, torch, lay
     """The whole canary-filled arena, guards included, equals a model after reconstruct and after
     recover: a call may write only bytes [0, L) of the shards it rebuilds, plus zeros to their
     16-byte boundary. (The rebuilt bytes are the originals: case 2 ties them to the reference.)"""
-    k, m, B = 40, 20, ARENA_B
+    run_wide_arena(fec, codec, oracle, torch, layout, L)
+
+
+def run_wide_arena(fec, codec, oracle, torch, layout, L, B=ARENA_B):
+    k, m = 40, 20
     n, R, slots = k + m, rup16(L), min(k, m)
-    rng = np.random.default_rng(L + len(layout))
-    kinds = np.array(([0, 1, 2, 7, 20, -1, 16, 17] * 9)[:B])
-    rng.shuffle(kinds)
-    present = np.ones((B, n), dtype=bool)
-    for b in range(B):
-        if kinds[b] >= 0:
-            present[b] = erase_block(rng, k, m, int(kinds[b]))
-        else:
-            present[b, pick(rng, range(n), m + 1, [int(rng.integers(0, k))])] = False
-    sh = encoded(oracle, rng, B, k, m, L)
-    data, par, out = arena_layout(layout, k, m, L, slots)
+    kinds, present, sh = arena_case(oracle, layout, L, B)
+    data, par, out = arena_layout(layout, k, m, L, slots, B)
     img = np.full(max(data.end(), par.end()) + GUARD, CANARY, dtype=np.uint8)
     dmg = damage(sh, present)
     img[data.idx(0, L)] = dmg[:, :k, :L]     # input slots hold canary bytes from L on
