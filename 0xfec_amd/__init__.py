@@ -53,6 +53,7 @@ FEC_MAX_DECODE_SHARDS = 32
 FEC_MAX_WIDE_SHARDS = 256
 FEC_LOCATE_CLEAN = -1
 FEC_LOCATE_UNKNOWN = -2
+FEC_LOCATE_TOO_FEW = -3
 FEC_LOCATE_MAX_BAD = 8
 
 _vp = ctypes.c_void_p
@@ -87,6 +88,7 @@ lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp
 lib.fec_rs_verify_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_locate_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i]
 lib.fec_rs_locate_multi_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i, _vp, _vp, _sz, _vp, _i]
+lib.fec_rs_locate_partial_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp, _vp, _i]
 lib.fec_rs_reconstruct_some_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
 lib.fec_rs_update_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
 lib.fec_rs_encode_idx_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
@@ -532,6 +534,38 @@ class Codec:
                               counts=None, shard_len=None):
         return self._locate_multi(k, m, _Layout(k, m, data, parity, _SOME), max_bad, bad_count, present_out, counts,
                                   shard_len)
+
+    # ---- locate-partial (FEC_DEVICE only; device tensors; m <= 16): rs_locate_multi for blocks that also
+    # have missing shards. masks is a 4-byte integer device tensor [B, W] of present
+    # masks, FEC_MASK_WORDS(k + m) <= W <= 8; bad_count also receives FEC_LOCATE_TOO_FEW; present_out has
+    # the masks' shape and may be masks itself; counts has three elements (located, unknown, too few);
+    # max_bad may be 0 (verify only).
+    def rs_locate_partial_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, present_mask, mask_words,
+                              max_bad, bad_count, present_out=None, counts=None, flags=FEC_DEVICE):
+        return lib.fec_rs_locate_partial_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                               present_mask, mask_words, max_bad, bad_count, present_out, counts,
+                                               flags)
+
+    def _locate_partial(self, k, m, lay, masks, max_bad, bad_count, present_out, counts, shard_len):
+        ma, W = self._col_masks(masks, lay.B)
+        pa = None
+        if present_out is not None:
+            pa, Wo = self._col_masks(present_out, lay.B)
+            assert Wo == W, "present_out has the masks' shape"
+        ca = None if counts is None else self._words_addr(counts, 3, "counts")
+        return _check(self.rs_locate_partial_raw(k, m, *lay.args(shard_len), ma, W, max_bad,
+                                                 self._words_addr(bad_count, lay.B, "bad_count"), pa, ca),
+                      "fec_rs_locate_partial_batch")
+
+    def rs_locate_partial(self, k, m, shards, masks, bad_count, max_bad=FEC_LOCATE_MAX_BAD, present_out=None,
+                          counts=None, shard_len=None):
+        return self._locate_partial(k, m, _Layout(k, m, shards, None, _SOME), masks, max_bad, bad_count, present_out,
+                                    counts, shard_len)
+
+    def rs_locate_partial_split(self, k, m, data, parity, masks, bad_count, max_bad=FEC_LOCATE_MAX_BAD,
+                                present_out=None, counts=None, shard_len=None):
+        return self._locate_partial(k, m, _Layout(k, m, data, parity, _SOME), masks, max_bad, bad_count, present_out,
+                                    counts, shard_len)
 
     def _reconstruct_some(self, k, m, lay, masks, want, status, shard_len):
         wa = None if want is None else self._words_addr(want, lay.B, "want")

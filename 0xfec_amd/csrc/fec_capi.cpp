@@ -452,7 +452,8 @@ struct Call {
     size_t mask_words = 1;
     int mask_n = 0;            // the shards a mask covers (0: k + m; the update calls' column masks: k)
     int max_m = -1;            // the call's largest m (-1: none; the locate-multi call: 16)
-    int max_bad = 1;           // the locate-multi call's max_bad, in [1, FEC_LOCATE_MAX_BAD]
+    int max_bad = 1;           // the locate-multi call's max_bad, in [min_bad, FEC_LOCATE_MAX_BAD]
+    int min_bad = 1;           // (the locate-partial call: 0)
     struct {
         const void *a, *b;
     } words[2] = {};           // (mask, status)-like pairs of 4-byte arrays, either may be null
@@ -477,7 +478,7 @@ static int check_call(fec_ctx* ctx, Call& c, Code** code) {
         return FEC_ERR_INVALID_ARG;
     if (s.len == 0) return FEC_ERR_SHARD_NO_DATA;
     if (s.len > (size_t(1) << 30) || c.out_slots <= 0) return FEC_ERR_INVALID_ARG;
-    if (c.max_bad < 1 || c.max_bad > FEC_LOCATE_MAX_BAD) return FEC_ERR_INVALID_ARG;
+    if (c.max_bad < c.min_bad || c.max_bad > FEC_LOCATE_MAX_BAD) return FEC_ERR_INVALID_ARG;
     if (c.wide && (c.mask_words < (size_t)FEC_MASK_WORDS(c.mask_n ? c.mask_n : c.k + c.m) || c.mask_words > 8))
         return FEC_ERR_INVALID_ARG;
     int rc = select_device(ctx);
@@ -651,6 +652,24 @@ int fec_rs_locate_multi_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
     return rs_locate_multi_device(ctx, code, {c.s, max_bad, bad_count, present_out, mask_words, counts});
+}
+
+// Locate-multi for blocks with missing shards: the same checks, max_bad = 0 allowed, the masks required.
+int fec_rs_locate_partial_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, const uint8_t* data,
+                                size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                                size_t shard_stride, const uint32_t* present_mask, size_t mask_words, int max_bad,
+                                int32_t* bad_count, uint32_t* present_out, uint32_t* counts, int flags) {
+    Call c{k, m, 256, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
+    c.null_arg = !bad_count || !present_mask;
+    c.max_m = fk::kLocateMultiRows, c.max_bad = max_bad, c.min_bad = 0;
+    c.wide = true, c.mask_words = mask_words;
+    c.words[0] = {present_mask, bad_count};
+    c.words[1] = {present_out, counts};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_locate_partial_device(ctx, code, {{c.s, max_bad, bad_count, present_out, mask_words, counts}, present_mask});
 }
 
 // ---------------------------------------------------------------- update, encode-idx

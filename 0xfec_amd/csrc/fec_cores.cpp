@@ -9,6 +9,7 @@
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
 #include "fec_locate_multi.hpp"
+#include "fec_locate_partial.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
 #include "fec_update.hpp"
@@ -458,6 +459,96 @@ int rs_locate_multi_device(fec_ctx* ctx, const Code* code, const LocateMultiCall
     });
 }
 
+// Locate-partial (fec_locate_partial.hip; LocatePartialCall, fec_ctx.hpp): locate-multi's cut, with a
+// slice's larger workspace (fec_locate_partial.hpp locate_partial_ws: a plan word and m PermTabs per
+// block on top of locate-multi's, and one line of zeros) held under kPlanBytes.
+static size_t locate_partial_per_launch(size_t nblocks, uint32_t cps, uint32_t words, uint32_t m) {
+    const size_t per_block = (size_t)(words + 2) * 4 + (cps + 7) / 8 + (size_t)m * sizeof(gf::PermTab);
+    return std::max<size_t>(1, std::min(blocks_per_launch(nblocks, cps), (kPlanBytes - 192) / per_block));
+}
+
+// What one slice of a locate-partial call runs, in order: `clear` bytes of the workspace set to zero,
+// the plan, the scan, the solve, the finalize.
+struct LocatePartialSlice {
+    size_t clear;
+    fk::LocatePartialPlanArgs plan;
+    fk::LocatePartialScanArgs scan;
+    fk::LocatePartialSolveArgs solve;
+    fk::LocatePartialFinArgs fin;
+};
+
+// run(slice) for every slice of a call whose workspace is at ws, until one fails. No device work
+// (fec__selftest_locate_partial_slices calls it without one).
+template <class R>
+static int locate_partial_launches(const Code* code, const LocatePartialCall& pc, uint8_t* ws, R run) {
+    const LocateMultiCall& c = pc.c;
+    const size_t nblocks = c.s.nblocks;
+    const uint32_t cps = chunks_of(c.s.len);
+    const uint32_t m = (uint32_t)code->m, n = (uint32_t)code->k + m, words = (n + 31) / 32;
+    return for_slices(nblocks, locate_partial_per_launch(nblocks, cps, words, m), [&](size_t b0, size_t nb) -> int {
+        const fk::PartialWs w = fk::locate_partial_ws(nb, cps, words, m);
+        const uint32_t* masks = pc.masks + b0 * c.mask_words;
+        LocatePartialSlice sl{};
+        sl.clear = w.plan;
+        fk::LocatePartialPlanArgs& p = sl.plan;
+        p.masks = masks;
+        p.plan = (uint32_t*)(ws + w.plan);
+        p.ltabs = (uint32_t*)(ws + w.ltabs);
+        p.nblocks = (uint32_t)nb;
+        p.k = (uint32_t)code->k;
+        p.m = m;
+        p.max_bad = (uint32_t)c.max_bad;
+        p.mask_words = (uint32_t)c.mask_words;
+        fk::LocatePartialScanArgs& a = sl.scan;
+        fill_syndrome(a, code, 0, c.s.blocks(b0, nb));   // (m <= 16)
+        a.bitmap = (uint64_t*)ws;
+        a.masks = masks;
+        a.plan = p.plan;
+        a.ltabs = p.ltabs;
+        a.atabs = code->d_lmtab;
+        a.zeros = ws + w.zeros;
+        a.mask_words = p.mask_words;
+        fk::LocatePartialSolveArgs& v = sl.solve;
+        v.s = a;
+        v.nwords = (uint32_t)(w.blk / sizeof(uint64_t));
+        v.n = n;
+        v.words = words;
+        v.ft = code->d_lmtab ? (const uint8_t*)(code->d_lmtab + (size_t)m * m * 8) : nullptr;   // (m = 0)
+        v.blk = (uint32_t*)(ws + w.blk);
+        fk::LocatePartialFinArgs& f = sl.fin;
+        f.blk = v.blk;
+        f.plan = p.plan;
+        f.masks = masks;
+        f.bad_count = c.bad_count + b0;
+        f.present = c.present ? c.present + b0 * c.mask_words : nullptr;
+        f.counts = c.counts;
+        f.nblocks = (uint32_t)nb;
+        f.n = n;
+        f.words = words;
+        f.mask_words = p.mask_words;
+        return run(sl);
+    });
+}
+
+// As rs_locate_multi_device: three counts set to 0 on the stream, each slice clears its workspace.
+int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartialCall& pc) {
+    const LocateMultiCall& c = pc.c;
+    const uint32_t cps = chunks_of(c.s.len);
+    const uint32_t m = (uint32_t)code->m, words = (uint32_t)(code->k + code->m + 31) / 32;
+    const size_t per = locate_partial_per_launch(c.s.nblocks, cps, words, m);
+    const int rc = grow_plans(ctx, fk::locate_partial_ws(per, cps, words, m).end);
+    if (rc) return rc;
+    if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 3 * sizeof(uint32_t), ctx->stream));
+    return locate_partial_launches(code, pc, ctx->work->d_plans, [&](const LocatePartialSlice& sl) -> int {
+        HIP_TRY(hipMemsetAsync(ctx->work->d_plans, 0, sl.clear, ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_partial_plan(sl.plan, ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_partial_scan(sl.scan, flat_grid(sl.scan.total), ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_partial_solve(sl.solve, ctx->stream));
+        HIP_TRY(fk::launch_rs_locate_partial_finalize(sl.fin, ctx->stream));
+        return FEC_OK;
+    });
+}
+
 // Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
 // the wide tile, storing into both regions.
 int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
@@ -869,6 +960,94 @@ int fec__selftest_locate_multi_slices(void) {
         return FEC_OK;
     });
     if (bad || slices != 3 || blocks != B) return 3;
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the slices of a locate-partial
+// call, for (k, m) = (5, 4), (5, 16), (5, 0) and (40, 16), 70 000-byte shards and one block more than
+// kPlanBytes of workspace holds (so two slices). Every slice's clear size, workspace parts (bitmap,
+// block words, zeros, plan words, scaling tables: each where the parts before it end), mask, data,
+// parity and output bases and the records' fields are compared with values worked out here. Then a
+// call without masks written or counts. 0 on success, else 1000 * (code index + 1) + 100 * slice + the
+// failing field.
+int fec__selftest_locate_partial_slices(void) {
+    const size_t L = 70000, cps = 4375, W = 3;
+    const size_t ss = 70016;
+    const uintptr_t in0 = uintptr_t(1) << 40, par0 = uintptr_t(3) << 40, mask0 = uintptr_t(4) << 40,
+                    tab0 = uintptr_t(5) << 40, cnt0 = uintptr_t(6) << 40, out0 = uintptr_t(7) << 40,
+                    lm0 = uintptr_t(8) << 40, ws0 = uintptr_t(9) << 40, pm0 = uintptr_t(10) << 40;
+    static const int codes[][3] = {{5, 4, 8}, {5, 16, 0}, {5, 0, 2}, {40, 16, 8}};   // k, m, max_bad
+    int ci = 0;
+    for (auto& cd : codes) {
+        const int base = 1000 * ++ci;
+        const int k = cd[0], m = cd[1];
+        const size_t words = (size_t)(k + m + 31) / 32;
+        const size_t per = std::min<size_t>(kMaxItems / cps,
+                                            (kPlanBytes - 192) / ((words + 2) * 4 + (cps + 7) / 8 + (size_t)m * 32));
+        const size_t B = per + 1, dbs = k * ss + 48, pbs = (size_t)m * ss + 32;
+        if (per >= (size_t)(kMaxItems / cps)) return base + 1;   // the workspace is the tighter limit here
+        FakeCode code;
+        code.k = k;
+        code.m = m;
+        code.d_tabs.p = (uint32_t*)tab0;
+        code.d_lmtab.p = (uint32_t*)lm0;
+        const LocatePartialCall c{{{L, B, (uint8_t*)in0, dbs, (uint8_t*)par0, pbs, ss, ss}, cd[2], (int32_t*)out0,
+                                   (uint32_t*)mask0, W, (uint32_t*)cnt0},
+                                  (const uint32_t*)pm0};
+        std::vector<LocatePartialSlice> got;
+        const int rc = locate_partial_launches(&code, c, (uint8_t*)ws0, [&](const LocatePartialSlice& sl) -> int {
+            got.push_back(sl);
+            return FEC_OK;
+        });
+        if (rc != FEC_OK || got.size() != 2) return base + 2;
+        for (size_t s = 0; s < 2; ++s) {
+            const LocatePartialSlice& sl = got[s];
+            const int fail = base + 100 * (int)s;
+            const size_t b0 = s * per, nb = s ? 1 : per;
+            const size_t bm = (nb * cps + 255) / 256 * 32, bw = (nb * (words + 1) * 4 + 15) / 16 * 16;
+            const size_t pw = (nb * 4 + 15) / 16 * 16;
+            const uintptr_t zero = ws0 + bm + bw, plan = zero + 64, lt = plan + pw;
+            if (sl.clear != bm + bw + 64 || lt - ws0 + nb * m * 32 > kPlanBytes) return fail + 3;
+            const fk::LocatePartialPlanArgs& p = sl.plan;
+            if ((uintptr_t)p.masks != pm0 + b0 * W * 4 || p.mask_words != W || p.nblocks != nb) return fail + 4;
+            if ((uintptr_t)p.plan != plan || (uintptr_t)p.ltabs != lt) return fail + 5;
+            if (p.k != (uint32_t)k || p.m != (uint32_t)m || p.max_bad != (uint32_t)cd[2]) return fail + 6;
+            const fk::LocatePartialScanArgs& a = sl.scan;
+            if ((uintptr_t)a.in != in0 + b0 * dbs || a.in_bs != dbs || a.ss != ss) return fail + 7;
+            if ((uintptr_t)a.par != par0 + b0 * pbs || a.par_bs != pbs) return fail + 8;
+            if (a.k != (uint32_t)k || a.m != (uint32_t)m || a.len != L || a.cps != cps) return fail + 9;
+            if (a.total != nb * cps || a.div_cps.d != cps) return fail + 10;
+            if ((uintptr_t)a.tabs != tab0 || (uintptr_t)a.bitmap != ws0 || (uintptr_t)a.atabs != lm0) return fail + 11;
+            if (a.masks != p.masks || a.plan != p.plan || a.ltabs != p.ltabs || a.mask_words != W) return fail + 12;
+            if ((uintptr_t)a.zeros != zero) return fail + 13;
+            const fk::LocatePartialSolveArgs& v = sl.solve;
+            if (memcmp(&v.s, &a, sizeof(a)) != 0) return fail + 14;
+            if (v.nwords != bm / 8 || v.n != (uint32_t)(k + m) || v.words != words) return fail + 15;
+            if ((uintptr_t)v.ft != lm0 + (size_t)m * m * 32 || (uintptr_t)v.blk != ws0 + bm) return fail + 16;
+            const fk::LocatePartialFinArgs& f = sl.fin;
+            if (f.blk != v.blk || f.plan != p.plan || f.masks != p.masks) return fail + 17;
+            if ((uintptr_t)f.bad_count != out0 + b0 * 4 || (uintptr_t)f.present != mask0 + b0 * W * 4) return fail + 18;
+            if ((uintptr_t)f.counts != cnt0 || f.nblocks != nb || f.n != v.n || f.words != words || f.mask_words != W)
+                return fail + 19;
+        }
+    }
+    // no masks written and no counts: none in any finalize; the masks read stride by mask_words
+    Code code;
+    code.k = 5;
+    code.m = 4;
+    const size_t per = (kPlanBytes - 192) / (12 + 1 + 128), B = per + 7;
+    const LocatePartialCall c{{{16, B, (uint8_t*)in0, 128, (uint8_t*)par0, 64, 16, 16}, 1, (int32_t*)out0, nullptr, 2,
+                               nullptr},
+                              (const uint32_t*)pm0};
+    size_t slices = 0, blocks = 0;
+    int bad = 0;
+    (void)locate_partial_launches(&code, c, (uint8_t*)ws0, [&](const LocatePartialSlice& sl) -> int {
+        if (sl.fin.present || sl.fin.counts || sl.plan.max_bad != 1 || sl.clear > kPlanBytes) ++bad;
+        if ((uintptr_t)sl.fin.masks != pm0 + blocks * 8 || (uintptr_t)sl.scan.in != in0 + blocks * 128) ++bad;
+        ++slices, blocks += sl.fin.nblocks;
+        return FEC_OK;
+    });
+    if (bad || slices != 2 || blocks != B) return 3;
     return 0;
 }
 

@@ -235,6 +235,13 @@ struct LocateMultiCall {
     uint32_t* counts;
 };
 int rs_locate_multi_device(fec_ctx* ctx, const Code* code, const LocateMultiCall& c);
+// Locate-partial (fec_locate_partial.hip): locate-multi's call with the blocks' present masks,
+// mask_words apart like the masks written (present may be masks itself).
+struct LocatePartialCall {
+    LocateMultiCall c;
+    const uint32_t* masks;
+};
+int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartialCall& c);
 int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, const Shards& s, const DecodeWords& w,
                                const uint32_t* want);
 int rs_encode_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,

@@ -11,6 +11,7 @@
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
 #include "fec_locate_multi.hpp"
+#include "fec_locate_partial.hpp"
 #include "fec_ragged.hpp"
 #include "fec_some.hpp"
 #include "fec_wide.hpp"
@@ -530,6 +531,263 @@ int fec__selftest_locate_multi(void) {
                 }
             }
         }
+    }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): the locate-partial call's
+// arithmetic (fec_locate_partial.hpp: the plan word, the scaling bytes, the scaled rows, the per-chunk
+// solver with its present set, the count; the functions the plan, scan, solve and finalize kernels
+// run) on real blocks. Per code one random codeword of three 16-byte chunks; per max_bad = 0 .. 8 and
+// erasure count e = 0 .. m + 1, 24 seeded blocks: a set of e missing shards (random; with shard 0; data
+// only; parity only, where there are enough), twelve error patterns on the present shards (none; one
+// bit; T_b shards in one byte column; T_b shards each in another chunk; supports {a,b} and {b,c}; the
+// first present shard among the corrupt; one shard, every byte; T_b + 1 in one column; T_b + 1 spread
+// over the chunks; t random shards; T_b < t <= (m - e) - T_b shards; up to T_b shards with several bytes
+// each), the missing shards then taken as zeros. The syndromes are those of that word under the code's
+// matrix. The result must be
+//   - too few for e > m, whatever the bytes;
+//   - 0 exactly when no present shard was changed and t <= m - e (the punctured code's distance);
+//   - exactly the t corrupt shards if t <= T_b, unknown if T_b < t <= (m - e) - T_b;
+//   - for n <= 12 the definition by brute force against the punctured generator: every set E of at
+//     most T_b present shards in ascending size, which explains the block if every byte column of the
+//     present shards outside E lies in the column space of the generator's rows outside E and X (at
+//     most one set of the smallest size may pass);
+//   - with a full mask and max_bad >= 1, what locate_multi_chunk / locate_multi_count give.
+// 0 on success, else 1000000 * (code index + 1) + 10000 * max_bad + 100 * e + case index + 1.
+int fec__selftest_locate_partial(void) {
+    static const int shapes[][2] = {{1, 2},   {2, 2},  {6, 3},    {3, 5},  {8, 4}, {16, 8},
+                                    {20, 10}, {4, 16}, {240, 16}, {31, 1}, {32, 0}};
+    constexpr int R = fk::kLocateMultiRows;
+    constexpr uint32_t C = 3, W = 16 * C, NW = fk::kLocateMultiWords;
+    uint64_t seed = 0xD1B54A32D192ED03ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    auto nzbyte = [&rnd]() -> uint8_t { return (uint8_t)(1 + rnd() % 255); };
+    const uint8_t* ft = reinterpret_cast<const uint8_t*>(&gf::kTables);
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix((int)k, (int)n);
+        if (M.empty()) return 1000000 * si;
+        const uint8_t* P = M.data() + (size_t)k * k;   // parity rows
+        uint8_t A[R * R] = {};
+        fk::locate_multi_table(A, k, m);
+        std::vector<gf::PermTab> At((size_t)m * m);
+        for (size_t i = 0; i < At.size(); ++i) At[i] = gf::make_permtab(A[i]);
+        // one codeword: shard r's bytes at CW[r * W ..]
+        std::vector<uint8_t> CW((size_t)n * W, 0);
+        for (uint32_t j = 0; j < k; ++j)
+            for (uint32_t x = 0; x < W; ++x) CW[j * W + x] = (uint8_t)rnd();
+        for (uint32_t i = 0; i < m; ++i)
+            for (uint32_t j = 0; j < k; ++j)
+                for (uint32_t x = 0; x < W; ++x) CW[(k + i) * W + x] ^= gf::mul(P[i * k + j], CW[j * W + x]);
+        // column r of [P | I]: what shard r's bytes add to the syndromes
+        auto col = [&](uint32_t r, uint32_t i) -> uint8_t { return r < k ? P[i * k + r] : (uint8_t)(r - k == i); };
+
+        for (uint32_t max_bad = 0; max_bad <= (uint32_t)fk::kLocateMaxBad; ++max_bad)
+            for (uint32_t e = 0; e <= m + 1 && e <= n; ++e)
+                for (int ci = 0; ci < 24; ++ci) {
+                    const int fail = 1000000 * si + 10000 * (int)max_bad + 100 * (int)e + ci + 1;
+                    // the missing shards
+                    std::vector<uint32_t> perm(n);
+                    for (uint32_t r = 0; r < n; ++r) perm[r] = r;
+                    for (uint32_t r = 0; r + 1 < n; ++r) std::swap(perm[r], perm[r + rnd() % (n - r)]);
+                    const int kind = ci / 6;   // 0 random, 1 with shard 0, 2 data first, 3 parity first
+                    if (kind == 1) std::swap(perm[0], *std::find(perm.begin(), perm.end(), 0u));
+                    if (kind == 2) std::stable_partition(perm.begin(), perm.end(), [&](uint32_t r) { return r < k; });
+                    if (kind == 3) std::stable_partition(perm.begin(), perm.end(), [&](uint32_t r) { return r >= k; });
+                    uint32_t mask[NW] = {};
+                    for (uint32_t i = e; i < n; ++i) mask[perm[i] >> 5] |= 1u << (perm[i] & 31u);
+                    if ((n & 31u) && (ci & 1)) mask[(n - 1) >> 5] |= ~fk::low_mask(n & 31u);   // bits at and above n: ignored
+                    const std::vector<uint32_t> pres(perm.begin() + e, perm.end());   // random order
+                    const uint32_t np = n - e;
+
+                    const uint32_t plan = fk::locate_partial_plan(mask, k, m, max_bad);
+                    if (fk::partial_missing(plan) != e || ((plan & fk::kPartialTooFew) != 0) != (e > m)) return fail;
+                    if (e > m) {
+                        uint32_t none[NW] = {};
+                        if (fk::locate_partial_count(plan, none, NW, false) != fk::kLocateTooFew) return fail;
+                        if (fk::locate_partial_count(plan, none, NW, true) != fk::kLocateTooFew) return fail;
+                        continue;
+                    }
+                    const uint32_t sums = m - e, T = fk::partial_radius(plan);
+                    if (T != std::min(max_bad, sums / 2)) return fail;
+
+                    // the word: the codeword with errors on present shards
+                    std::vector<uint8_t> Y(CW);
+                    std::vector<uint8_t> hit(n, 0);
+                    auto err = [&](uint32_t r, uint32_t x, uint8_t v) {   // present shard r, byte x ^= v
+                        if (hit[r] & (1u << (x / 16))) return;
+                        hit[r] |= (uint8_t)(1u << (x / 16));
+                        Y[r * W + x] ^= v;
+                    };
+                    auto some = [&](uint32_t t) { return std::min(t, np); };
+                    const uint32_t x0 = rnd() % 16, x1 = 16 + rnd() % 16;
+                    switch (ci % 12) {
+                        case 0: break;
+                        case 1:
+                            if (np) err(pres[0], rnd() % W, (uint8_t)(1u << (rnd() % 8)));
+                            break;
+                        case 2:
+                            for (uint32_t i = 0; i < some(T); ++i) err(pres[i], x1, nzbyte());
+                            break;
+                        case 3:
+                            for (uint32_t i = 0; i < some(T); ++i) err(pres[i], 16 * (i % C) + rnd() % 16, nzbyte());
+                            break;
+                        case 4:
+                            if (np > 0) err(pres[0], x0, nzbyte());
+                            if (np > 1) err(pres[1], x0, nzbyte()), err(pres[1], x1, nzbyte());
+                            if (np > 2) err(pres[2], x1, nzbyte());
+                            break;
+                        case 5: {
+                            const uint32_t first = *std::min_element(pres.begin(), pres.end());
+                            err(first, x1, nzbyte());
+                            for (uint32_t i = 0, left = T ? T - 1 : 0; i < np && left; ++i)
+                                if (pres[i] != first) err(pres[i], x1, nzbyte()), --left;
+                            break;
+                        }
+                        case 6:
+                            for (uint32_t x = 0; x < W; ++x) err(pres[0], x, nzbyte()), hit[pres[0]] = 0;
+                            hit[pres[0]] = 7;
+                            break;
+                        case 7:
+                            for (uint32_t i = 0; i < some(T + 1); ++i) err(pres[i], x0, nzbyte());
+                            break;
+                        case 8:
+                            for (uint32_t i = 0; i < some(T + 1); ++i) err(pres[i], 16 * (i % C) + x0, nzbyte());
+                            break;
+                        case 9:
+                            for (uint32_t i = 0, t = rnd() % (np + 1); i < t; ++i) err(pres[i], rnd() % W, nzbyte());
+                            break;
+                        case 10:
+                            if (sums >= 2 * T + 1)
+                                for (uint32_t i = 0, t = T + 1 + rnd() % (sums - 2 * T); i < some(t); ++i)
+                                    err(pres[i], x1, nzbyte());
+                            break;
+                        default:
+                            for (uint32_t i = 0, t = T ? 1 + rnd() % T : 0; i < some(t); ++i)
+                                for (uint32_t c = 0; c < C; ++c) err(pres[i], 16 * c + rnd() % 16, nzbyte());
+                    }
+                    uint32_t t = 0;
+                    uint32_t hitset[NW] = {};
+                    for (uint32_t r = 0; r < n; ++r)
+                        if (hit[r]) ++t, hitset[r >> 5] |= 1u << (r & 31u);
+                    for (uint32_t i = 0; i < e; ++i) memset(&Y[perm[i] * W], 0, W);   // missing: zeros
+
+                    // the syndromes of the word: the codeword's are zero, so those of the shards that differ
+                    std::vector<uint8_t> S((size_t)m * W, 0);
+                    for (uint32_t r = 0; r < n; ++r)
+                        if (hit[r] || !fk::partial_has(mask, r))
+                            for (uint32_t i = 0; i < m; ++i)
+                                for (uint32_t x = 0; x < W; ++x)
+                                    S[i * W + x] ^= gf::mul(col(r, i), (uint8_t)(Y[r * W + x] ^ CW[r * W + x]));
+
+                    // the code under test: the block's scaling tables, then chunk by chunk
+                    gf::PermTab Lt[R] = {};
+                    for (uint32_t i = 0; i < m; ++i) Lt[i] = gf::make_permtab_fast(fk::locate_partial_scale(mask, k, n, i));
+                    uint32_t sup[NW] = {};
+                    bool unknown = false, flagged = false;
+                    for (uint32_t c = 0; c < C; ++c) {
+                        uint32_t acc[R][4] = {};
+                        for (uint32_t i = 0; i < m; ++i) memcpy(acc[i], &S[i * W + 16 * c], 16);
+                        if (e) fk::locate_partial_scale_rows<R>(acc, m, Lt);
+                        uint32_t cs[NW] = {};
+                        if (fk::locate_partial_chunk<R>(acc, m, plan, n, At.data(), ft, mask, cs)) unknown = true;
+                        for (uint32_t w = 0; w < NW; ++w) sup[w] |= cs[w];
+                        // the scan's test: the OR of the first m - e sums of the scaled rows
+                        uint32_t any = 0;
+                        for (uint32_t l = 0; l < sums; ++l) {
+                            uint32_t w[4] = {};
+                            for (uint32_t i = 0; i < m; ++i)
+                                for (uint32_t d = 0; d < 4; ++d) w[d] ^= fk::locate_mul4(At[l * m + i], acc[i][d]);
+                            any |= w[0] | w[1] | w[2] | w[3];
+                        }
+                        flagged = flagged || any != 0;
+                    }
+                    const int32_t got = fk::locate_partial_count(plan, sup, NW, unknown);
+                    if ((got == 0) != !flagged) return fail;   // an unflagged block is never solved
+
+                    // the guarantees
+                    if (t == 0 && got != 0) return fail;
+                    if (t > 0 && t <= sums && got == 0) return fail;
+                    if (t <= T && (got != (int32_t)t || memcmp(sup, hitset, sizeof(sup)) != 0)) return fail;
+                    if (t > T && t + T <= sums && got != fk::kLocateUnknown) return fail;
+                    for (uint32_t i = 0; i < e; ++i)
+                        if (got > 0 && (sup[perm[i] >> 5] >> (perm[i] & 31u)) & 1u) return fail;   // never a missing shard
+
+                    // the definition
+                    if (n <= 12) {
+                        // whether the columns of the rows `rows` of Y lie in the column space of those rows of M
+                        auto explains = [&](const std::vector<uint32_t>& rows) -> bool {
+                            const uint32_t nr = (uint32_t)rows.size(), wd = k + W;
+                            std::vector<uint8_t> G((size_t)nr * wd);
+                            for (uint32_t i = 0; i < nr; ++i) {
+                                memcpy(&G[i * wd], &M[(size_t)rows[i] * k], k);
+                                memcpy(&G[i * wd + k], &Y[rows[i] * W], W);
+                            }
+                            uint32_t row = 0;
+                            for (uint32_t j = 0; j < k && row < nr; ++j) {
+                                uint32_t p = row;
+                                while (p < nr && G[p * wd + j] == 0) ++p;
+                                if (p == nr) continue;
+                                for (uint32_t x = 0; x < wd; ++x) std::swap(G[p * wd + x], G[row * wd + x]);
+                                const uint8_t pi = gf::inv(G[row * wd + j]);
+                                for (uint32_t i = row + 1; i < nr; ++i) {
+                                    const uint8_t f = gf::mul(G[i * wd + j], pi);
+                                    if (f)
+                                        for (uint32_t x = j; x < wd; ++x) G[i * wd + x] ^= gf::mul(f, G[row * wd + x]);
+                                }
+                                ++row;
+                            }
+                            for (uint32_t i = row; i < nr; ++i)
+                                for (uint32_t x = k; x < wd; ++x)
+                                    if (G[i * wd + x]) return false;
+                            return true;
+                        };
+                        std::vector<uint32_t> sorted(pres);
+                        std::sort(sorted.begin(), sorted.end());
+                        int32_t want = fk::kLocateUnknown;
+                        uint32_t wantset[NW] = {};
+                        for (uint32_t v = 0; v <= T && want == fk::kLocateUnknown; ++v) {
+                            int found = 0;
+                            for (uint32_t bits = 0; bits < (1u << np); ++bits) {   // np <= 12
+                                uint32_t cnt = 0;
+                                for (uint32_t b = bits; b; b &= b - 1) ++cnt;
+                                if (cnt != v) continue;
+                                std::vector<uint32_t> rows;
+                                for (uint32_t i = 0; i < np; ++i)
+                                    if (!((bits >> i) & 1u)) rows.push_back(sorted[i]);
+                                if (!explains(rows)) continue;
+                                ++found, want = (int32_t)v;
+                                memset(wantset, 0, sizeof(wantset));
+                                for (uint32_t i = 0; i < np; ++i)
+                                    if ((bits >> i) & 1u) wantset[sorted[i] >> 5] |= 1u << (sorted[i] & 31u);
+                            }
+                            if (found > 1) return fail;   // (distance m - e + 1 > 2 T_b rules it out)
+                        }
+                        if (got != want) return fail;
+                        if (want > 0 && memcmp(sup, wantset, sizeof(sup)) != 0) return fail;
+                    }
+
+                    // a full mask: the complete blocks' functions
+                    if (e == 0 && max_bad >= 1) {
+                        uint32_t sup2[NW] = {};
+                        bool unk2 = false;
+                        for (uint32_t c = 0; c < C; ++c) {
+                            uint32_t acc[R][4] = {};
+                            for (uint32_t i = 0; i < m; ++i) memcpy(acc[i], &S[i * W + 16 * c], 16);
+                            if (fk::locate_multi_chunk<R>(acc, m, n, T, At.data(), ft, sup2)) unk2 = true;
+                        }
+                        const int32_t got2 = fk::locate_multi_count(sup2, NW, unk2, T);
+                        if (got2 != got || (got > 0 && memcmp(sup, sup2, sizeof(sup)) != 0)) return fail;
+                    }
+                }
     }
     return 0;
 }

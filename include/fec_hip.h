@@ -30,6 +30,9 @@
  *                               and verify again), and the present mask that heals the block
  *   fec_rs_locate_multi_batch   no counterpart: up to m/2 corrupt shards of a block that fails Verify, the
  *                               radius of the code, and the present mask that heals the block (m <= 16)
+ *   fec_rs_locate_partial_batch no counterpart: the same for a block that also has missing shards, to the
+ *                               radius (m - e) / 2 that its e missing shards leave; the present mask
+ *                               then rebuilds the missing and the corrupt shards in one go (m <= 16)
  *   fec_rs_reconstruct_some_batch
  *                               Encoder.Reconstruct (want_mask NULL) and Encoder.ReconstructSome, in
  *                               place: missing parity shards are rebuilt too (klauspost's interface;
@@ -384,7 +387,9 @@ int fec_rs_locate_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
  * Cost. A clean batch is read once, no atomic is issued and nothing is written but the outputs; a
  * bitmap clear and one launch over the bitmap come on top of fec_rs_locate_batch's work. Only the
  * chunks that hold a nonzero syndrome are read again and solved, one lane per chunk: a batch with
- * many corrupt chunks takes several times fec_rs_locate_batch's time. */
+ * many corrupt chunks takes several times fec_rs_locate_batch's time.
+ *
+ * fec_rs_locate_partial_batch (below) takes blocks that also have missing shards. */
 #define FEC_LOCATE_MAX_BAD 8
 int fec_rs_locate_multi_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
                               const uint8_t *data, size_t data_block_stride,
@@ -392,6 +397,63 @@ int fec_rs_locate_multi_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size
                               size_t shard_stride, int max_bad, int32_t *bad_count,
                               uint32_t *present_out, size_t mask_words,
                               uint32_t *counts, int flags);
+
+/* Locate corrupt shards in blocks that also have missing shards: fec_rs_locate_multi_batch with a
+ * present mask per block. Regions, layouts, alignment rules and FEC_DEVICE-only are those of
+ * fec_rs_locate_multi_batch; only bytes [0, shard_len) of each present shard's slot count, and the
+ * contents of a missing shard's slot never influence any output (no byte of it is read).
+ *
+ *   present_mask  (required) device memory, 4-byte aligned: block b's mask is mask_words words in the
+ *                 wide calls' bit order (bit i % 32 of word i / 32 set: shard i is present); bits at
+ *                 and above k + m are ignored
+ *   mask_words    strides present_mask and present_out alike; FEC_MASK_WORDS(k + m) <= mask_words <= 8,
+ *                 else FEC_ERR_INVALID_ARG
+ *
+ * Per block b let e_b be the number of clear bits below k + m and T_b = min(max_bad, (m - e_b) / 2) its
+ * radius. The present shards of a block form a code of distance m - e_b + 1. bad_count[b] receives
+ *   FEC_LOCATE_TOO_FEW   e_b > m: fewer than k shards are present; the block's shards are not examined
+ *   0                    some codeword agrees with every present shard over bytes [0, shard_len). With
+ *                        e_b == m this is vacuous: any k shards determine a codeword
+ *   |E_b| in [1, T_b]    E_b is the smallest set of present shards, |E_b| <= T_b, whose replacement
+ *                        alone makes the present shards consistent; it is unique (m - e_b + 1 > 2 T_b)
+ *                        and is the union over byte columns of each column's unique error vector of
+ *                        weight <= T_b
+ *   FEC_LOCATE_UNKNOWN   the present shards are inconsistent and no such set exists; with T_b == 0
+ *                        every inconsistent block
+ * t corrupt present shards with t <= T_b are always located exactly; with T_b < t <= (m - e_b) - T_b the
+ * block is always unknown; beyond that a wrong set can be named. max_bad lies in [0,
+ * FEC_LOCATE_MAX_BAD]; 0 makes the call a verify of blocks with missing shards (results 0, unknown or
+ * too few). With every mask full and max_bad >= 1 the results, masks and counts[0..1] are those of
+ * fec_rs_locate_multi_batch block for block, and counts[2] is 0.
+ *
+ * Outputs, all device memory, 4-byte aligned (else FEC_ERR_ALIGNMENT); the call sets every word of
+ * each:
+ *   bad_count    (required) nblocks results
+ *   present_out  (optional) nblocks x mask_words words: the block's present bits below k + m, less the
+ *                bits of E_b for a located block, unchanged for every other block; bits at and above
+ *                k + m zero. It may be the same pointer as present_mask (exact aliasing only: the
+ *                masks are then updated in place); any other overlap is undefined. These masks go
+ *                straight into fec_rs_reconstruct_some_batch (k + m <= 32, mask_words == 1) or
+ *                fec_rs_reconstruct_wide_batch, which rebuilds the missing and the located shards in
+ *                one go (the wide call: the data shards among them; parity is then re-encoded):
+ *                e_b + |E_b| <= m leaves k shards present
+ *   counts       (optional) three uint32: when the call's work completes on the stream, [0] holds the
+ *                located blocks, [1] the unknown ones, [2] those with too few shards
+ * Nothing else is written. A result is not an error: the sticky word is untouched and fec_sync()
+ * returns FEC_OK after any mix of results. The scratch memory (fec_rs_locate_multi_batch's, and one
+ * word and m 32-byte tables per block) is the ctx's workspace.
+ *
+ * Scope: k >= 1, 0 <= m <= 16, k + m <= 256. The host-side checks come in fec_rs_locate_multi_batch's
+ * order: shard counts, k + m > 256, m > 16, flags, shard_len, max_bad, mask_words, the ctx,
+ * nblocks == 0 (FEC_OK, nothing touched), null pointers (bad_count, present_mask, data, and parity when
+ * m > 0), the layouts, the word alignment of the four word arrays. */
+#define FEC_LOCATE_TOO_FEW (-3)
+int fec_rs_locate_partial_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nblocks,
+                                const uint8_t *data, size_t data_block_stride,
+                                const uint8_t *parity, size_t parity_block_stride,
+                                size_t shard_stride, const uint32_t *present_mask, size_t mask_words,
+                                int max_bad, int32_t *bad_count, uint32_t *present_out,
+                                uint32_t *counts, int flags);
 
 /* RS Reconstruct / ReconstructSome, in place: as fec_rs_reconstruct_batch (k + m <=
  * FEC_MAX_DECODE_SHARDS, one uint32 present mask per block), but missing PARITY shards are rebuilt
