@@ -387,12 +387,19 @@ int rs_locate_device(fec_ctx* ctx, const Code* code, const LocateCall& c) {
         });
 }
 
-// Locate-multi (fec_locate_multi.hip; LocateMultiCall, fec_ctx.hpp). A batch is cut as the encode
-// cuts it (kMaxItems items per slice), and so that a slice's workspace (locate_multi_ws_bytes: one
-// bitmap bit per item, words + 1 words per block) stays under kPlanBytes.
-static size_t locate_multi_per_launch(size_t nblocks, uint32_t cps, uint32_t words) {
-    const size_t per_block = (size_t)(words + 1) * 4 + (cps + 7) / 8;   // (+ 47 bytes of rounding per slice)
-    return std::max<size_t>(1, std::min(blocks_per_launch(nblocks, cps), (kPlanBytes - 64) / per_block));
+// Locate-multi (fec_locate_multi.hip; LocateMultiCall, fec_ctx.hpp) and locate-partial
+// (fec_locate_partial.hip; LocatePartialCall). A batch is cut as the encode cuts it (kMaxItems items per
+// slice), and so that a slice's workspace stays under kPlanBytes: locate_multi_ws_bytes (one bitmap bit
+// per item, words + 1 words per block), and for locate-partial `block_extra` bytes per block and
+// `slice_extra` per slice on top (fec_locate_partial.hpp locate_partial_ws).
+static size_t locate_multi_per_launch(size_t nblocks, uint32_t cps, uint32_t words, size_t block_extra = 0,
+                                      size_t slice_extra = 0) {
+    const size_t per_block = (size_t)(words + 1) * 4 + (cps + 7) / 8 + block_extra;   // (+ 47 bytes of rounding per slice)
+    return std::max<size_t>(1, std::min(blocks_per_launch(nblocks, cps), (kPlanBytes - 64 - slice_extra) / per_block));
+}
+// locate-partial's: a plan word and m PermTabs per block; the line of zeros and the plan words' rounding.
+static size_t locate_partial_per_launch(size_t nblocks, uint32_t cps, uint32_t words, uint32_t m) {
+    return locate_multi_per_launch(nblocks, cps, words, 4 + (size_t)m * sizeof(gf::PermTab), 128);
 }
 
 // What one slice of a locate-multi call runs, in order: `clear` bytes of the workspace set to zero, the
@@ -404,69 +411,6 @@ struct LocateMultiSlice {
     fk::LocateMultiFinArgs fin;
 };
 
-// run(slice) for every slice of a call whose workspace is at ws, until one fails. No device work
-// (fec__selftest_locate_multi_slices calls it without one).
-template <class R>
-static int locate_multi_launches(const Code* code, const LocateMultiCall& c, uint8_t* ws, R run) {
-    const size_t nblocks = c.s.nblocks;
-    const uint32_t cps = chunks_of(c.s.len);
-    const uint32_t n = (uint32_t)(code->k + code->m), words = (n + 31) / 32;
-    const uint32_t T = fk::locate_multi_radius((uint32_t)code->m, (uint32_t)c.max_bad);
-    return for_slices(nblocks, locate_multi_per_launch(nblocks, cps, words), [&](size_t b0, size_t nb) -> int {
-        LocateMultiSlice sl{};
-        sl.clear = fk::locate_multi_ws_bytes(nb, cps, words);
-        fk::LocateMultiScanArgs& a = sl.scan;
-        fill_syndrome(a, code, 0, c.s.blocks(b0, nb));   // (m <= 16)
-        a.bitmap = (uint64_t*)ws;
-        fk::LocateMultiSolveArgs& v = sl.solve;
-        v.s = a;
-        v.nwords = (uint32_t)(fk::locate_multi_bitmap_bytes((uint64_t)nb * cps) / sizeof(uint64_t));
-        v.n = n;
-        v.T = T;
-        v.words = words;
-        v.atabs = code->d_lmtab;
-        v.ft = code->d_lmtab ? (const uint8_t*)(code->d_lmtab + (size_t)code->m * code->m * 8) : nullptr;   // (m = 0)
-        v.blk = (uint32_t*)(ws + fk::locate_multi_bitmap_bytes((uint64_t)nb * cps));
-        fk::LocateMultiFinArgs& f = sl.fin;
-        f.blk = v.blk;
-        f.bad_count = c.bad_count + b0;
-        f.present = c.present ? c.present + b0 * c.mask_words : nullptr;
-        f.counts = c.counts;
-        f.nblocks = (uint32_t)nb;
-        f.n = n;
-        f.T = T;
-        f.words = words;
-        f.mask_words = (uint32_t)c.mask_words;
-        return run(sl);
-    });
-}
-
-// The counts are set to 0 on the stream, as verify presets its count; each slice clears its workspace,
-// which is the stream's (ctx->work), so slices and calls on one stream follow one another in it.
-int rs_locate_multi_device(fec_ctx* ctx, const Code* code, const LocateMultiCall& c) {
-    const uint32_t cps = chunks_of(c.s.len);
-    const uint32_t words = (uint32_t)(code->k + code->m + 31) / 32;
-    const size_t per = locate_multi_per_launch(c.s.nblocks, cps, words);
-    const int rc = grow_plans(ctx, fk::locate_multi_ws_bytes(per, cps, words));
-    if (rc) return rc;
-    if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 2 * sizeof(uint32_t), ctx->stream));
-    return locate_multi_launches(code, c, ctx->work->d_plans, [&](const LocateMultiSlice& sl) -> int {
-        HIP_TRY(hipMemsetAsync(ctx->work->d_plans, 0, sl.clear, ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_multi_scan(sl.scan, flat_grid(sl.scan.total), ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_multi_solve(sl.solve, ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_multi_finalize(sl.fin, ctx->stream));
-        return FEC_OK;
-    });
-}
-
-// Locate-partial (fec_locate_partial.hip; LocatePartialCall, fec_ctx.hpp): locate-multi's cut, with a
-// slice's larger workspace (fec_locate_partial.hpp locate_partial_ws: a plan word and m PermTabs per
-// block on top of locate-multi's, and one line of zeros) held under kPlanBytes.
-static size_t locate_partial_per_launch(size_t nblocks, uint32_t cps, uint32_t words, uint32_t m) {
-    const size_t per_block = (size_t)(words + 2) * 4 + (cps + 7) / 8 + (size_t)m * sizeof(gf::PermTab);
-    return std::max<size_t>(1, std::min(blocks_per_launch(nblocks, cps), (kPlanBytes - 192) / per_block));
-}
-
 // What one slice of a locate-partial call runs, in order: `clear` bytes of the workspace set to zero,
 // the plan, the scan, the solve, the finalize.
 struct LocatePartialSlice {
@@ -477,21 +421,66 @@ struct LocatePartialSlice {
     fk::LocatePartialFinArgs fin;
 };
 
+// What the slices of both calls hold alike, for blocks [b0, b0 + nb) of the call and the workspace at
+// ws (the scan's bitmap first, the blocks' words behind it): the scan's flat launch and bitmap, the
+// solve's and the finalize's fields but for the radius (locate-multi's) and the plan and masks
+// (locate-partial's). solve.s is the caller's to copy from the scan once that is complete.
+template <class Slice>
+static void fill_locate_slice(Slice& sl, const Code* code, const LocateMultiCall& c, uint8_t* ws, size_t b0, size_t nb) {
+    const uint32_t m = (uint32_t)code->m, n = (uint32_t)code->k + m, words = (n + 31) / 32;
+    const size_t bitmap = fk::locate_multi_bitmap_bytes((uint64_t)nb * chunks_of(c.s.len));
+    fill_syndrome(sl.scan, code, 0, c.s.blocks(b0, nb));   // (m <= 16)
+    sl.scan.bitmap = (uint64_t*)ws;
+    sl.solve.nwords = (uint32_t)(bitmap / sizeof(uint64_t));
+    sl.solve.n = n;
+    sl.solve.words = words;
+    sl.solve.ft = code->d_lmtab ? (const uint8_t*)(code->d_lmtab + (size_t)m * m * 8) : nullptr;   // (m = 0)
+    sl.solve.blk = (uint32_t*)(ws + bitmap);
+    sl.fin.blk = sl.solve.blk;
+    sl.fin.bad_count = c.bad_count + b0;
+    sl.fin.present = c.present ? c.present + b0 * c.mask_words : nullptr;
+    sl.fin.counts = c.counts;
+    sl.fin.nblocks = (uint32_t)nb;
+    sl.fin.n = n;
+    sl.fin.words = words;
+    sl.fin.mask_words = (uint32_t)c.mask_words;
+}
+
 // run(slice) for every slice of a call whose workspace is at ws, until one fails. No device work
-// (fec__selftest_locate_partial_slices calls it without one).
+// (fec__selftest_locate_multi_slices calls it without one).
+template <class R>
+static int locate_multi_launches(const Code* code, const LocateMultiCall& c, uint8_t* ws, R run) {
+    const size_t nblocks = c.s.nblocks;
+    const uint32_t cps = chunks_of(c.s.len);
+    const uint32_t words = (uint32_t)(code->k + code->m + 31) / 32;
+    const uint32_t T = fk::locate_multi_radius((uint32_t)code->m, (uint32_t)c.max_bad);
+    return for_slices(nblocks, locate_multi_per_launch(nblocks, cps, words), [&](size_t b0, size_t nb) -> int {
+        LocateMultiSlice sl{};
+        sl.clear = fk::locate_multi_ws_bytes(nb, cps, words);
+        fill_locate_slice(sl, code, c, ws, b0, nb);
+        sl.solve.s = sl.scan;
+        sl.solve.T = T;
+        sl.solve.atabs = code->d_lmtab;
+        sl.fin.T = T;
+        return run(sl);
+    });
+}
+
+// As locate_multi_launches, for a locate-partial call (fec__selftest_locate_partial_slices): on top of
+// what both calls hold, the plan launch, the masks, and the workspace's parts behind the blocks' words.
 template <class R>
 static int locate_partial_launches(const Code* code, const LocatePartialCall& pc, uint8_t* ws, R run) {
     const LocateMultiCall& c = pc.c;
     const size_t nblocks = c.s.nblocks;
     const uint32_t cps = chunks_of(c.s.len);
-    const uint32_t m = (uint32_t)code->m, n = (uint32_t)code->k + m, words = (n + 31) / 32;
+    const uint32_t m = (uint32_t)code->m, words = (uint32_t)(code->k + code->m + 31) / 32;
     return for_slices(nblocks, locate_partial_per_launch(nblocks, cps, words, m), [&](size_t b0, size_t nb) -> int {
         const fk::PartialWs w = fk::locate_partial_ws(nb, cps, words, m);
-        const uint32_t* masks = pc.masks + b0 * c.mask_words;
         LocatePartialSlice sl{};
         sl.clear = w.plan;
+        fill_locate_slice(sl, code, c, ws, b0, nb);
         fk::LocatePartialPlanArgs& p = sl.plan;
-        p.masks = masks;
+        p.masks = pc.masks + b0 * c.mask_words;
         p.plan = (uint32_t*)(ws + w.plan);
         p.ltabs = (uint32_t*)(ws + w.ltabs);
         p.nblocks = (uint32_t)nb;
@@ -500,53 +489,62 @@ static int locate_partial_launches(const Code* code, const LocatePartialCall& pc
         p.max_bad = (uint32_t)c.max_bad;
         p.mask_words = (uint32_t)c.mask_words;
         fk::LocatePartialScanArgs& a = sl.scan;
-        fill_syndrome(a, code, 0, c.s.blocks(b0, nb));   // (m <= 16)
-        a.bitmap = (uint64_t*)ws;
-        a.masks = masks;
+        a.masks = p.masks;
         a.plan = p.plan;
         a.ltabs = p.ltabs;
         a.atabs = code->d_lmtab;
         a.zeros = ws + w.zeros;
         a.mask_words = p.mask_words;
-        fk::LocatePartialSolveArgs& v = sl.solve;
-        v.s = a;
-        v.nwords = (uint32_t)(w.blk / sizeof(uint64_t));
-        v.n = n;
-        v.words = words;
-        v.ft = code->d_lmtab ? (const uint8_t*)(code->d_lmtab + (size_t)m * m * 8) : nullptr;   // (m = 0)
-        v.blk = (uint32_t*)(ws + w.blk);
-        fk::LocatePartialFinArgs& f = sl.fin;
-        f.blk = v.blk;
-        f.plan = p.plan;
-        f.masks = masks;
-        f.bad_count = c.bad_count + b0;
-        f.present = c.present ? c.present + b0 * c.mask_words : nullptr;
-        f.counts = c.counts;
-        f.nblocks = (uint32_t)nb;
-        f.n = n;
-        f.words = words;
-        f.mask_words = p.mask_words;
+        sl.solve.s = a;
+        sl.fin.plan = p.plan;
+        sl.fin.masks = p.masks;
         return run(sl);
     });
 }
 
-// As rs_locate_multi_device: three counts set to 0 on the stream, each slice clears its workspace.
-int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartialCall& pc) {
-    const LocateMultiCall& c = pc.c;
-    const uint32_t cps = chunks_of(c.s.len);
-    const uint32_t m = (uint32_t)code->m, words = (uint32_t)(code->k + code->m + 31) / 32;
-    const size_t per = locate_partial_per_launch(c.s.nblocks, cps, words, m);
-    const int rc = grow_plans(ctx, fk::locate_partial_ws(per, cps, words, m).end);
+static int launch_locate_slice(const LocateMultiSlice& sl, hipStream_t s) {
+    HIP_TRY(fk::launch_rs_locate_multi_scan(sl.scan, flat_grid(sl.scan.total), s));
+    HIP_TRY(fk::launch_rs_locate_multi_solve(sl.solve, s));
+    HIP_TRY(fk::launch_rs_locate_multi_finalize(sl.fin, s));
+    return FEC_OK;
+}
+static int launch_locate_slice(const LocatePartialSlice& sl, hipStream_t s) {
+    HIP_TRY(fk::launch_rs_locate_partial_plan(sl.plan, s));
+    HIP_TRY(fk::launch_rs_locate_partial_scan(sl.scan, flat_grid(sl.scan.total), s));
+    HIP_TRY(fk::launch_rs_locate_partial_solve(sl.solve, s));
+    HIP_TRY(fk::launch_rs_locate_partial_finalize(sl.fin, s));
+    return FEC_OK;
+}
+
+// A call on the device: the stream's workspace (ctx->work) grown to ws_bytes, the call's `ncounts`
+// counts set to 0 on the stream, as verify presets its count, then launches(ws, run) with a run that
+// clears the slice's part of the workspace and queues its launches. The workspace is the stream's, so
+// slices and calls on one stream follow one another in it.
+template <class L>
+static int locate_slices_device(fec_ctx* ctx, size_t ws_bytes, uint32_t* counts, size_t ncounts, L launches) {
+    const int rc = grow_plans(ctx, ws_bytes);
     if (rc) return rc;
-    if (c.counts) HIP_TRY(hipMemsetAsync(c.counts, 0, 3 * sizeof(uint32_t), ctx->stream));
-    return locate_partial_launches(code, pc, ctx->work->d_plans, [&](const LocatePartialSlice& sl) -> int {
+    if (counts) HIP_TRY(hipMemsetAsync(counts, 0, ncounts * sizeof(uint32_t), ctx->stream));
+    return launches(ctx->work->d_plans, [&](const auto& sl) -> int {
         HIP_TRY(hipMemsetAsync(ctx->work->d_plans, 0, sl.clear, ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_partial_plan(sl.plan, ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_partial_scan(sl.scan, flat_grid(sl.scan.total), ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_partial_solve(sl.solve, ctx->stream));
-        HIP_TRY(fk::launch_rs_locate_partial_finalize(sl.fin, ctx->stream));
-        return FEC_OK;
+        return launch_locate_slice(sl, ctx->stream);
     });
+}
+
+int rs_locate_multi_device(fec_ctx* ctx, const Code* code, const LocateMultiCall& c) {
+    const uint32_t cps = chunks_of(c.s.len);
+    const uint32_t words = (uint32_t)(code->k + code->m + 31) / 32;
+    const size_t per = locate_multi_per_launch(c.s.nblocks, cps, words);
+    return locate_slices_device(ctx, fk::locate_multi_ws_bytes(per, cps, words), c.counts, 2,
+                                [&](uint8_t* ws, auto run) { return locate_multi_launches(code, c, ws, run); });
+}
+
+int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartialCall& pc) {
+    const uint32_t cps = chunks_of(pc.c.s.len);
+    const uint32_t m = (uint32_t)code->m, words = (uint32_t)(code->k + code->m + 31) / 32;
+    const size_t per = locate_partial_per_launch(pc.c.s.nblocks, cps, words, m);
+    return locate_slices_device(ctx, fk::locate_partial_ws(per, cps, words, m).end, pc.c.counts, 3,
+                                [&](uint8_t* ws, auto run) { return locate_partial_launches(code, pc, ws, run); });
 }
 
 // Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then

@@ -180,12 +180,11 @@ hipError_t launch_rs_locate_multi_scan(const LocateMultiScanArgs& a, int grid, h
 hipError_t launch_rs_locate_multi_solve(const LocateMultiSolveArgs& a, hipStream_t s) {
     if (a.nwords == 0 || a.s.m == 0) return hipSuccess;
     const uint32_t grid = (a.nwords + kThreads - 1) / kThreads;
-    const size_t fixed = sizeof(gf::Tables) + (size_t)a.s.m * a.s.m * sizeof(gf::PermTab);
-    const size_t code = (size_t)a.s.m * a.s.k * sizeof(gf::PermTab);
-    if (fixed + code <= kLocateMultiSolveLds)
-        hipLaunchKernelGGL(rs_locate_multi_solve_kernel<true>, dim3(grid), dim3(kThreads), fixed + code, s, a);
+    const LocateSolveLds lds = locate_solve_lds(a.s.k, a.s.m);
+    if (lds.tabs)
+        hipLaunchKernelGGL(rs_locate_multi_solve_kernel<true>, dim3(grid), dim3(kThreads), lds.bytes, s, a);
     else
-        hipLaunchKernelGGL(rs_locate_multi_solve_kernel<false>, dim3(grid), dim3(kThreads), fixed, s, a);
+        hipLaunchKernelGGL(rs_locate_multi_solve_kernel<false>, dim3(grid), dim3(kThreads), lds.bytes, s, a);
     return hipGetLastError();
 }
 

@@ -70,18 +70,27 @@ struct LocateMultiSums {
     }
 };
 
+// Bit r of a block's present mask (the wide calls' bit order).
+GF_HD inline bool partial_has(const uint32_t* mask, uint32_t r) { return (mask[r >> 5] >> (r & 31u)) & 1u; }
+
 // One byte column: its m power sums W, some of them nonzero. For v = 1 .. T: solve the v x v Hankel
 // system [W_{i+j}] sigma = [W_{v+i}] (singular: next v), require the recurrence for every
 // l <= m - 1 - v, and require v distinct roots among the points 0 .. n - 1. The first v that passes
 // gives the column's unique error vector of weight <= T; its support is ORed into sup and the result
 // is true. No v passes: false (the column has no explanation of weight <= T).
 // v = 1, the common case, needs no elimination and no search: sigma_0 = W_1 / W_0 is the root itself.
-template <class FT>
+// MASKED (locate-partial, fec_locate_partial.hpp: a block with missing shards): m is the number of
+// sums the column has, m - e, and `mask` the block's present mask; a root counts only at a present
+// shard, so a candidate with a root at a missing point, or too few roots among the present ones, is
+// rejected. Not MASKED: `mask` is not read. (A compile-time flag and a defaulted trailing argument:
+// the instances without the flag compile to the code they had before the flag existed.)
+template <bool MASKED = false, class FT>
 GF_HD inline bool locate_multi_column(const LocateMultiSums& W, uint32_t m, uint32_t n, uint32_t T, FT ft,
-                                      uint32_t (&sup)[kLocateMultiWords]) {
+                                      uint32_t (&sup)[kLocateMultiWords], const uint32_t* mask = nullptr) {
     if (T >= 1 && W[0] != 0) {
         const uint32_t r = lm_mul(ft, W[1], lm_inv(ft, W[0]));
         bool ok = r < n;
+        if constexpr (MASKED) ok = ok && partial_has(mask, r);
         for (uint32_t l = 1; l + 1 < m && ok; ++l) ok = lm_mul(ft, r, W[l]) == W[l + 1];
         if (ok) {
 #pragma unroll
@@ -128,7 +137,9 @@ GF_HD inline bool locate_multi_column(const LocateMultiSums& W, uint32_t m, uint
         for (uint32_t r = 0; r < n; ++r) {
             uint32_t acc = 1;   // Horner, sigma_v = 1
             for (uint32_t j = v; j-- > 0;) acc = lm_mul(ft, acc, r) ^ M[j][v];
-            if (acc == 0) roots[r >> 5] |= 1u << (r & 31u), ++count;
+            bool root = acc == 0;
+            if constexpr (MASKED) root = root && partial_has(mask, r);
+            if (root) roots[r >> 5] |= 1u << (r & 31u), ++count;
         }
         if (count != v) continue;
         for (uint32_t w = 0; w < kLocateMultiWords; ++w) sup[w] |= roots[w];
@@ -141,17 +152,22 @@ GF_HD inline bool locate_multi_column(const LocateMultiSums& W, uint32_t m, uint
 // zeroed): the power sums by the code's coefficient PermTabs A (row l's at A + l * m), then every
 // nonzero byte column. The supports found are ORed into sup; true if a column has no explanation of
 // weight <= T (the block is unknown then).
+// MASKED (a block with e missing shards, S its scaled syndromes: fec_locate_partial.hpp): only the
+// first `sums` = m - e rows of A are applied, T is the block's own radius, and the columns are solved
+// with `sums` sums under the block's present mask `mask`. Not MASKED: neither is read.
 // (always inlined: as a called function it would take S through memory)
-template <int ROWS, class FT>
+template <int ROWS, bool MASKED = false, class FT>
 GF_HD inline __attribute__((always_inline)) bool locate_multi_chunk(const uint32_t (&S)[ROWS][4], uint32_t m, uint32_t n, uint32_t T,
-                                     const gf::PermTab* A, FT ft, uint32_t (&sup)[kLocateMultiWords]) {
+                                     const gf::PermTab* A, FT ft, uint32_t (&sup)[kLocateMultiWords],
+                                     uint32_t sums = 0, const uint32_t* mask = nullptr) {
     static_assert(ROWS <= 16, "a column's power sums are packed in 16 bytes");
+    const uint32_t ns = MASKED ? sums : m;   // the column's sums
     // unrolled over ROWS with uniform predicates, so that S and the sums keep to registers
     uint32_t Wd[ROWS][4];
 #pragma unroll
     for (int l = 0; l < ROWS; ++l) {
         uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-        if (l < (int)m) {
+        if (l < (int)ns) {
 #pragma unroll
             for (int i = 0; i < ROWS; ++i)
                 if (i < (int)m) {
@@ -168,7 +184,8 @@ GF_HD inline __attribute__((always_inline)) bool locate_multi_chunk(const uint32
         LocateMultiSums W = {{0, 0, 0, 0}};
 #pragma unroll
         for (int l = 0; l < ROWS; ++l) W.w[l >> 2] |= ((Wd[l][x >> 2] >> (8 * (x & 3))) & 0xFFu) << (8 * (l & 3));
-        if ((W.w[0] | W.w[1] | W.w[2] | W.w[3]) != 0 && !locate_multi_column(W, m, n, T, ft, sup)) unknown = true;
+        if ((W.w[0] | W.w[1] | W.w[2] | W.w[3]) != 0 && !locate_multi_column<MASKED>(W, ns, n, T, ft, sup, mask))
+            unknown = true;
     }
     return unknown;
 }
@@ -227,5 +244,18 @@ inline size_t locate_multi_ws_bytes(uint64_t nblocks, uint32_t cps, uint32_t wor
 hipError_t launch_rs_locate_multi_scan(const LocateMultiScanArgs& a, int grid, hipStream_t s);
 hipError_t launch_rs_locate_multi_solve(const LocateMultiSolveArgs& a, hipStream_t s);
 hipError_t launch_rs_locate_multi_finalize(const LocateMultiFinArgs& a, hipStream_t s);
+
+// The LDS of a solve workgroup (locate-multi's and locate-partial's): the field's tables and the m x m
+// coefficient PermTabs, and the code's m x k PermTabs beside them (`tabs`) where all fit.
+struct LocateSolveLds {
+    size_t bytes;
+    bool tabs;
+};
+inline LocateSolveLds locate_solve_lds(uint32_t k, uint32_t m) {
+    const size_t fixed = sizeof(gf::Tables) + (size_t)m * m * sizeof(gf::PermTab);
+    const size_t code = (size_t)m * k * sizeof(gf::PermTab);
+    const bool tabs = fixed + code <= kLocateMultiSolveLds;
+    return {tabs ? fixed + code : fixed, tabs};
+}
 
 }  // namespace fk

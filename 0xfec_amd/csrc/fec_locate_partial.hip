@@ -118,7 +118,8 @@ __global__ __launch_bounds__(kThreads) void rs_locate_partial_scan_kernel(Locate
 
 // rs_locate_multi_solve_kernel with each lane's own block plan: the syndromes again under the mask,
 // scaled where the block has missing shards, then m - e sums solved to the block's radius with roots
-// at present shards only.
+// at present shards only (that kernel's solver, MASKED). The text around the lane's work repeats that
+// kernel's: every shared form of it changed that kernel's machine code (Locate-partial).
 template <bool LDS_TABS>
 __global__ __launch_bounds__(kThreads) void rs_locate_partial_solve_kernel(LocatePartialSolveArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -175,7 +176,8 @@ __global__ __launch_bounds__(kThreads) void rs_locate_partial_solve_kernel(Locat
             }
             if (partial_missing(p.plan) != 0)
                 locate_partial_scale_rows<kLocateMultiRows>(acc, m, reinterpret_cast<const gf::PermTab*>(a.s.ltabs) + (uint64_t)b * m);
-            unknown = locate_partial_chunk<kLocateMultiRows>(acc, m, p.plan, a.n, atabs, ft, p.mask, sup);
+            unknown = locate_multi_chunk<kLocateMultiRows, true>(acc, m, a.n, partial_radius(p.plan), atabs, ft, sup,
+                                                                 m - partial_missing(p.plan), p.mask);
         }
         uint64_t todo = bits;
         while (todo) {
@@ -266,12 +268,11 @@ hipError_t launch_rs_locate_partial_scan(const LocatePartialScanArgs& a, int gri
 hipError_t launch_rs_locate_partial_solve(const LocatePartialSolveArgs& a, hipStream_t s) {
     if (a.nwords == 0 || a.s.m == 0) return hipSuccess;
     const uint32_t grid = (a.nwords + kThreads - 1) / kThreads;
-    const size_t fixed = sizeof(gf::Tables) + (size_t)a.s.m * a.s.m * sizeof(gf::PermTab);
-    const size_t code = (size_t)a.s.m * a.s.k * sizeof(gf::PermTab);
-    if (fixed + code <= kLocateMultiSolveLds)
-        hipLaunchKernelGGL(rs_locate_partial_solve_kernel<true>, dim3(grid), dim3(kThreads), fixed + code, s, a);
+    const LocateSolveLds lds = locate_solve_lds(a.s.k, a.s.m);
+    if (lds.tabs)
+        hipLaunchKernelGGL(rs_locate_partial_solve_kernel<true>, dim3(grid), dim3(kThreads), lds.bytes, s, a);
     else
-        hipLaunchKernelGGL(rs_locate_partial_solve_kernel<false>, dim3(grid), dim3(kThreads), fixed, s, a);
+        hipLaunchKernelGGL(rs_locate_partial_solve_kernel<false>, dim3(grid), dim3(kThreads), lds.bytes, s, a);
     return hipGetLastError();
 }
 

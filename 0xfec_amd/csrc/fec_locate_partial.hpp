@@ -10,13 +10,16 @@
 // present shards are a code of the same kind with m - e checks and multipliers u'_r = u_r lambda(r):
 //   W'_l = sum_{j <= e} lambda_j V_{l+j} = sum_{r present} u'_r r^l y_r          for l < m - e,
 // all zero exactly when some codeword agrees with every present shard, and sum_{r in E} (u'_r eps_r) r^l
-// for errors E among the present shards: what locate_multi_column solves, with m - e for m.
+// for errors E among the present shards: what locate_multi_column (fec_locate_multi.hpp, the one solver
+// of both calls) solves, with m - e for m.
 // Since A[l][i] = u_{k+i} (k+i)^l,  sum_j lambda_j A[l+j][i] = A[l][i] lambda(k+i), so
 //   W'_l = sum_{i < m} A[l][i] (lambda(k+i) s_i):
 // a block's plan is the m bytes lambda(k+i), the kernels scale syndrome row i by its byte and then
 // apply the first m - e rows of the code's own table. lambda(k+i) is zero for a missing parity shard,
 // whose row counts for nothing. A root of a column's locator at a missing point is no shard the caller
-// holds: such a candidate is rejected (locate_partial_column).
+// holds: such a candidate is rejected. The solve kernel and the self-test therefore call
+// locate_multi_chunk<ROWS, true> with the scaled syndromes, m - e sums, the block's radius and its
+// present mask (the solver's MASKED form); this header has no solver of its own.
 #pragma once
 
 #include "fec_locate_multi.hpp"
@@ -30,9 +33,6 @@ constexpr int32_t kLocateTooFew = -3;   // FEC_LOCATE_TOO_FEW
 constexpr uint32_t kPartialTooFew = 1u << 31;
 GF_HD inline uint32_t partial_missing(uint32_t plan) { return plan & 0x1FFu; }
 GF_HD inline uint32_t partial_radius(uint32_t plan) { return (plan >> 16) & 0xFu; }
-
-// Bit r of a block's present mask (the wide calls' bit order).
-GF_HD inline bool partial_has(const uint32_t* mask, uint32_t r) { return (mask[r >> 5] >> (r & 31u)) & 1u; }
 
 // The plan word of a block from its present mask; bits at and above n = k + m are ignored.
 GF_HD inline uint32_t locate_partial_plan(const uint32_t* mask, uint32_t k, uint32_t m, uint32_t max_bad) {
@@ -54,71 +54,6 @@ GF_HD inline uint8_t locate_partial_scale(const uint32_t* mask, uint32_t k, uint
     return prod;
 }
 
-// locate_multi_column (fec_locate_multi.hpp) for a block with missing shards, its sibling and not that
-// function with one more argument, so that the complete blocks' kernels keep their machine code: the
-// column's `sums` = m - e sums W, v = 1 .. T as there, and a root counts only at a present shard. A
-// candidate with a root at a missing point, or too few roots among the present ones, is rejected.
-template <class FT>
-GF_HD inline bool locate_partial_column(const LocateMultiSums& W, uint32_t sums, uint32_t n, uint32_t T, FT ft,
-                                        const uint32_t* mask, uint32_t (&sup)[kLocateMultiWords]) {
-    if (T >= 1 && W[0] != 0) {
-        const uint32_t r = lm_mul(ft, W[1], lm_inv(ft, W[0]));
-        bool ok = r < n && partial_has(mask, r);
-        for (uint32_t l = 1; l + 1 < sums && ok; ++l) ok = lm_mul(ft, r, W[l]) == W[l + 1];
-        if (ok) {
-#pragma unroll
-            for (uint32_t w = 0; w < kLocateMultiWords; ++w) sup[w] |= w == r >> 5 ? 1u << (r & 31u) : 0u;
-            return true;
-        }
-    }
-    for (uint32_t v = 2; v <= T; ++v) {   // 2 v - 1 <= sums - 1: every W index below is in range
-        uint8_t M[kLocateMaxBad][kLocateMaxBad + 1];
-        for (uint32_t i = 0; i < v; ++i) {
-            for (uint32_t j = 0; j < v; ++j) M[i][j] = W[i + j];
-            M[i][v] = W[v + i];
-        }
-        bool singular = false;
-        for (uint32_t c = 0; c < v && !singular; ++c) {   // Gauss-Jordan
-            uint32_t p = c;
-            while (p < v && M[p][c] == 0) ++p;
-            if (p == v) {
-                singular = true;
-                break;
-            }
-            const uint32_t pi = lm_inv(ft, M[p][c]);
-            for (uint32_t j = 0; j <= v; ++j) {
-                const uint8_t t = (uint8_t)lm_mul(ft, M[p][j], pi);
-                M[p][j] = M[c][j];
-                M[c][j] = t;
-            }
-            for (uint32_t i = 0; i < v; ++i) {
-                const uint32_t f = M[i][c];
-                if (i == c || f == 0) continue;
-                for (uint32_t j = 0; j <= v; ++j) M[i][j] ^= (uint8_t)lm_mul(ft, f, M[c][j]);
-            }
-        }
-        if (singular) continue;
-        bool ok = true;
-        for (uint32_t l = v; l + v < sums && ok; ++l) {
-            uint32_t acc = W[l + v];
-            for (uint32_t j = 0; j < v; ++j) acc ^= lm_mul(ft, M[j][v], W[l + j]);
-            ok = acc == 0;
-        }
-        if (!ok) continue;
-        uint32_t roots[kLocateMultiWords] = {0, 0, 0, 0, 0, 0, 0, 0};
-        uint32_t count = 0;
-        for (uint32_t r = 0; r < n; ++r) {
-            uint32_t acc = 1;   // Horner, sigma_v = 1
-            for (uint32_t j = v; j-- > 0;) acc = lm_mul(ft, acc, r) ^ M[j][v];
-            if (acc == 0 && partial_has(mask, r)) roots[r >> 5] |= 1u << (r & 31u), ++count;
-        }
-        if (count != v) continue;
-        for (uint32_t w = 0; w < kLocateMultiWords; ++w) sup[w] |= roots[w];
-        return true;
-    }
-    return false;
-}
-
 // Syndrome row i times the block's byte lambda(k + i), by its PermTab L[i].
 template <int ROWS>
 GF_HD inline __attribute__((always_inline)) void locate_partial_scale_rows(uint32_t (&S)[ROWS][4], uint32_t m, const gf::PermTab* L) {
@@ -129,41 +64,6 @@ GF_HD inline __attribute__((always_inline)) void locate_partial_scale_rows(uint3
 #pragma unroll
             for (int d = 0; d < 4; ++d) S[i][d] = locate_mul4(t, S[i][d]);
         }
-}
-
-// locate_multi_chunk for a block with missing shards, from its scaled syndromes S: the block's m - e
-// sums W' by the first m - e rows of A, then every nonzero byte column to the block's radius.
-template <int ROWS, class FT>
-GF_HD inline __attribute__((always_inline)) bool locate_partial_chunk(const uint32_t (&S)[ROWS][4], uint32_t m, uint32_t plan, uint32_t n,
-                                       const gf::PermTab* A, FT ft, const uint32_t* mask,
-                                       uint32_t (&sup)[kLocateMultiWords]) {
-    static_assert(ROWS <= 16, "a column's power sums are packed in 16 bytes");
-    const uint32_t sums = m - partial_missing(plan), T = partial_radius(plan);
-    uint32_t Wd[ROWS][4];
-#pragma unroll
-    for (int l = 0; l < ROWS; ++l) {
-        uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-        if (l < (int)sums) {
-#pragma unroll
-            for (int i = 0; i < ROWS; ++i)
-                if (i < (int)m) {
-                    const gf::PermTab t = A[(uint32_t)l * m + (uint32_t)i];
-                    w0 ^= locate_mul4(t, S[i][0]), w1 ^= locate_mul4(t, S[i][1]);
-                    w2 ^= locate_mul4(t, S[i][2]), w3 ^= locate_mul4(t, S[i][3]);
-                }
-        }
-        Wd[l][0] = w0, Wd[l][1] = w1, Wd[l][2] = w2, Wd[l][3] = w3;
-    }
-    bool unknown = false;
-#pragma unroll
-    for (int x = 0; x < 16; ++x) {
-        LocateMultiSums W = {{0, 0, 0, 0}};
-#pragma unroll
-        for (int l = 0; l < ROWS; ++l) W.w[l >> 2] |= ((Wd[l][x >> 2] >> (8 * (x & 3))) & 0xFFu) << (8 * (l & 3));
-        if ((W.w[0] | W.w[1] | W.w[2] | W.w[3]) != 0 && !locate_partial_column(W, sums, n, T, ft, mask, sup))
-            unknown = true;
-    }
-    return unknown;
 }
 
 // A block's result: too few shards before anything else, then locate_multi_count with the block's radius.

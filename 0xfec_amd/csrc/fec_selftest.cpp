@@ -536,9 +536,9 @@ int fec__selftest_locate_multi(void) {
 }
 
 // Internal self-test (not part of the public ABI, no device needed): the locate-partial call's
-// arithmetic (fec_locate_partial.hpp: the plan word, the scaling bytes, the scaled rows, the per-chunk
-// solver with its present set, the count; the functions the plan, scan, solve and finalize kernels
-// run) on real blocks. Per code one random codeword of three 16-byte chunks; per max_bad = 0 .. 8 and
+// arithmetic (fec_locate_partial.hpp: the plan word, the scaling bytes, the scaled rows, the count;
+// fec_locate_multi.hpp: the per-chunk solver with a present set; the functions the plan, scan, solve
+// and finalize kernels run) on real blocks. Per code one random codeword of three 16-byte chunks; per max_bad = 0 .. 8 and
 // erasure count e = 0 .. m + 1, 24 seeded blocks: a set of e missing shards (random; with shard 0; data
 // only; parity only, where there are enough), twelve error patterns on the present shards (none; one
 // bit; T_b shards in one byte column; T_b shards each in another chunk; supports {a,b} and {b,c}; the
@@ -698,7 +698,7 @@ int fec__selftest_locate_partial(void) {
                         for (uint32_t i = 0; i < m; ++i) memcpy(acc[i], &S[i * W + 16 * c], 16);
                         if (e) fk::locate_partial_scale_rows<R>(acc, m, Lt);
                         uint32_t cs[NW] = {};
-                        if (fk::locate_partial_chunk<R>(acc, m, plan, n, At.data(), ft, mask, cs)) unknown = true;
+                        if (fk::locate_multi_chunk<R, true>(acc, m, n, T, At.data(), ft, cs, sums, mask)) unknown = true;
                         for (uint32_t w = 0; w < NW; ++w) sup[w] |= cs[w];
                         // the scan's test: the OR of the first m - e sums of the scaled rows
                         uint32_t any = 0;
