@@ -1,8 +1,10 @@
 """The guarded arena of the device oracle tests (test_gpu_*.py): a batch lives in one canary-filled
 byte image with guards at both ends, its shard slots placed by regions with slack and gaps, and after
 a call the WHOLE image is compared with a model. Here: the regions, the device layouts, the image, the
-comparison, the encoded batch that verify, locate and locate-multi start from, and the fixtures the
-test modules import by name. test_arena.py checks this module on the CPU.
+comparison, the encoded batch that verify, locate and locate-multi start from (encoded_arena: parity
+by the device's encode; oracle_arena: the same image with the oracle's parity, built without a device,
+which test_gpu_row_sweep.py starts from), and the fixtures the test modules import by name.
+test_arena.py checks this module on the CPU.
 """
 import numpy as np
 import pytest
@@ -146,6 +148,21 @@ def encoded_arena(codec, fec, torch, layout, k, m, L, B, rng):
         pad = par.index(L, rup16(L))
         assert (img[pad] == 0).all()
         img[pad] = CANARY
+    return img, data, par
+
+
+def oracle_arena(oracle, layout, k, m, L, B, rng):
+    """encoded_arena without a device: the same regions, canaries and data bytes (the same draws from
+    rng), the parity over [0, L) taken from oracle.rs_encode, canary from L on. A test that starts from
+    this image does not rest on the library's own encode."""
+    data, par = place(layout, k, m, L, B)
+    img = canary_image([data, par])
+    sh = np.zeros((B, k + m, L), dtype=np.uint8)
+    sh[:, :k] = rng.integers(0, 256, (B, k, L), dtype=np.uint8)
+    img[data.index(0, L)] = sh[:, :k]
+    if m:
+        oracle.rs_encode(k, m, sh)
+        img[par.index(0, L)] = sh[:, k:]
     return img, data, par
 
 

@@ -13,6 +13,8 @@ replacement of s alone explains every syndrome, else it is unknown. Every block 
 consequences are asserted without the model: one corrupt shard with m >= 2 is located, and t corrupt
 shards with 2 <= t < m give unknown.
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -66,13 +68,16 @@ def model_verdicts(oracle, gf, k, m, shards, L):
 
 
 class Batch:
-    """An encoded batch in an arena, corrupted per block by pattern, with the calls that locate it."""
+    """An encoded batch in an arena, corrupted per block by pattern, with the calls that locate it.
+    build(layout, k, m, L, B, rng) makes the encoded arena: encoded_arena by default, arena.oracle_arena for
+    test_gpu_row_sweep.py."""
 
-    def __init__(self, codec, fec, torch, oracle, gf, layout, k, m, L, B, seed, patterns=None):
+    def __init__(self, codec, fec, torch, oracle, gf, layout, k, m, L, B, seed, patterns=None, build=None):
         self.codec, self.fec, self.torch, self.oracle, self.gf = codec, fec, torch, oracle, gf
         self.k, self.m, self.n, self.L, self.B = k, m, k + m, L, B
         self.rng = rng = np.random.default_rng(seed)
-        img, self.data, self.par = encoded_arena(codec, fec, torch, layout, k, m, L, B, rng)
+        build = build or functools.partial(encoded_arena, codec, fec, torch)
+        img, self.data, self.par = build(layout, k, m, L, B, rng)
         self.clean = img.copy()
         self.clean.setflags(write=False)
         self.P = oracle.build_matrix(k, k + m)[k:] if m else None

@@ -17,6 +17,7 @@ build_matrix. With T = min(max_bad, m // 2):
     gives the expectation: exactly the corrupt shards for t <= T, unknown above.
 Every block is compared; the theorem's two consequences are asserted for the small codes as well.
 """
+import functools
 import itertools
 
 import numpy as np
@@ -95,9 +96,12 @@ def model_brute(oracle, gf, k, m, T, shards, L):
 
 
 class Batch:
-    """An encoded batch in an arena, corrupted per block by pattern, with the calls that locate it."""
+    """An encoded batch in an arena, corrupted per block by pattern, with the calls that locate it.
+    build(layout, k, m, L, B, rng) makes the encoded arena: encoded_arena by default, arena.oracle_arena for
+    test_gpu_row_sweep.py."""
 
-    def __init__(self, codec, fec, torch, oracle, gf, layout, k, m, L, B, seed, max_bad=MAX_BAD, patterns=None):
+    def __init__(self, codec, fec, torch, oracle, gf, layout, k, m, L, B, seed, max_bad=MAX_BAD, patterns=None,
+                 build=None):
         self.codec, self.fec, self.torch, self.oracle, self.gf = codec, fec, torch, oracle, gf
         self.k, self.m, self.n, self.L, self.B = k, m, k + m, L, B
         self.max_bad = max_bad
@@ -106,7 +110,8 @@ class Batch:
         # larger codes: at most m - T corrupt shards per block (m = 0: nothing can be inconsistent)
         self.cap = self.n if self.brute or m == 0 else m - T
         self.rng = rng = np.random.default_rng(seed)
-        img, self.data, self.par = encoded_arena(codec, fec, torch, layout, k, m, L, B, rng)
+        build = build or functools.partial(encoded_arena, codec, fec, torch)
+        img, self.data, self.par = build(layout, k, m, L, B, rng)
         self.clean = img.copy()
         self.clean.setflags(write=False)
         self.hit = [set() for _ in range(B)]      # the shards of each block with a changed byte in [0, L)

@@ -20,6 +20,7 @@ build_matrix. With e_b missing shards and T_b = min(max_bad, (m - e_b) // 2):
     expectation: exactly the corrupt shards for t <= T_b, unknown above.
 Every block is compared, for bad_count, present_out and the three counts.
 """
+import functools
 import itertools
 
 import numpy as np
@@ -68,15 +69,19 @@ def model_brute(oracle, gf, k, m, T, present, y, L):
 
 
 class PBatch(Batch):
-    """An encoded batch with missing shards per block by kind and corrupt present shards by pattern."""
+    """An encoded batch with missing shards per block by kind and corrupt present shards by pattern.
+    build(layout, k, m, L, B, rng) makes the encoded arena: encoded_arena by default, arena.oracle_arena for
+    test_gpu_row_sweep.py."""
 
-    def __init__(self, codec, fec, torch, oracle, gf, layout, k, m, L, B, seed, patterns=None, kinds=None):
+    def __init__(self, codec, fec, torch, oracle, gf, layout, k, m, L, B, seed, patterns=None, kinds=None,
+                 build=None):
         self.codec, self.fec, self.torch, self.oracle, self.gf = codec, fec, torch, oracle, gf
         self.k, self.m, self.n, self.L, self.B = k, m, k + m, L, B
         self.max_bad = MAX_BAD
         self.brute = self.n <= BRUTE_N
         self.rng = rng = np.random.default_rng(seed)
-        img, self.data, self.par = encoded_arena(codec, fec, torch, layout, k, m, L, B, rng)
+        build = build or functools.partial(encoded_arena, codec, fec, torch)
+        img, self.data, self.par = build(layout, k, m, L, B, rng)
         self.clean = img.copy()
         self.clean.setflags(write=False)
         self.kinds = kinds or [(b * 3 + 1) % NKINDS for b in range(B)]           # neighbours differ

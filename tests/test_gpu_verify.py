@@ -9,6 +9,7 @@ The statuses are reduced per block, not per wave or workgroup: 67 blocks of shor
 blocks into one wave, 70 000-byte shards spread one block over 18 workgroups, and the batch cut into
 two launches puts one block alone into the second.
 """
+import functools
 import os
 import re
 
@@ -28,12 +29,15 @@ LAYOUTS = ["interleaved", "split"]
 
 
 class Batch:
-    """An encoded batch in an arena on the host (img) with the calls to verify a flipped copy of it."""
+    """An encoded batch in an arena on the host (img) with the calls to verify a flipped copy of it.
+    build(layout, k, m, L, B, rng) makes the arena: encoded_arena by default, arena.oracle_arena for
+    test_gpu_row_sweep.py."""
 
-    def __init__(self, codec, fec, torch, layout, k, m, L, B, seed):
+    def __init__(self, codec, fec, torch, layout, k, m, L, B, seed, build=None):
         self.codec, self.fec, self.torch = codec, fec, torch
         self.k, self.m, self.L, self.B = k, m, L, B
-        img, self.data, self.par = encoded_arena(codec, fec, torch, layout, k, m, L, B, np.random.default_rng(seed))
+        build = build or functools.partial(encoded_arena, codec, fec, torch)
+        img, self.data, self.par = build(layout, k, m, L, B, np.random.default_rng(seed))
         img.setflags(write=False)
         self.img = img
 

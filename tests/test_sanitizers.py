@@ -9,6 +9,7 @@
   program: validation paths on the CPU, full GPU round trips on the box.
 """
 import os
+import resource
 import subprocess
 
 import pytest
@@ -44,7 +45,13 @@ def test_fuzz_wire_parsers(tmp_path):
     corpus = tmp_path / "corpus"
     corpus.mkdir()
     _seeds(corpus)
-    p = subprocess.run([fz, "-runs=400000", "-max_len=2048", "-seed=4077", str(corpus)],
+    # libFuzzer limits the target's peak RSS (2048 MB by default), and a child starts with the peak of
+    # the process that forked it (ru_maxrss survives fork and exec): the limit stands on top of this
+    # process's own peak, which under tools/cpu_tests_sanitized.sh is about 2 GB by the time this runs.
+    # The limit on one malloc stays at the default.
+    own = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss // 1024 + 1
+    p = subprocess.run([fz, "-runs=400000", "-max_len=2048", "-seed=4077", "-rss_limit_mb=%d" % (2048 + own),
+                        "-malloc_limit_mb=2048", str(corpus)],
                        capture_output=True, text=True, timeout=300, env=san_env(gpu=False), cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-4000:]
     assert "Done 400000 runs" in p.stderr
