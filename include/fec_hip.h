@@ -57,6 +57,15 @@
  * 16)) of an output shard slot are also written, as zeros (whole 16-byte stores), and
  * nothing past that is touched. FEC_HOST writes exactly shard_len bytes per output.
  *
+ * Distances (FEC_DEVICE). Strides and offsets are 64-bit throughout: the block strides, the
+ * distance between any two regions (data, parity, out, old data; parity may lie below the data)
+ * and a block's or shard's offset from its base may be any value that the alignment rules admit,
+ * beyond 2^32 included; the regions of one call need not lie in one allocation. One limit: the
+ * calls that rebuild shards (fec_rs_reconstruct_batch, fec_rs_recover_batch, their wide and ragged
+ * forms, fec_rs_reconstruct_some_batch) take shard strides below 2^32 and return
+ * FEC_ERR_INVALID_ARG for a shard_stride of 2^32 or more, before anything is enqueued. Every other
+ * call takes any shard stride.
+ *
  * Memory kinds (`flags`):
  *   FEC_DEVICE  pointers are device memory of the ctx's device; shard_stride, block
  *               strides and base pointers must be multiples of 16, every shard slot

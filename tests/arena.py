@@ -173,3 +173,24 @@ def shards(img, data, par):
     if par.rows:
         out[:, data.rows:] = img[par.index(0, data.ss)]
     return out
+
+
+# ---------------------------------------------------------------- models shared by the near and the far tests
+
+def recover_statuses(fec, e_d, few, slots):
+    """What a recover call reports per block: the erased data shards rebuilt, or why none was."""
+    return np.where(e_d == 0, 0, np.where(few, fec.FEC_ERR_TOO_FEW_SHARDS,
+                                          np.where(e_d > slots, fec.FEC_ERR_INVALID_ARG, e_d)))
+
+
+def folded_parity(oracle, k, m, delta, cols, parity):
+    """Update / encode-idx: parity [B, m, L] ^ the oracle's encode of delta [B, k, L] with every column
+    outside cols (bool [B, k]) zero; blocks with no column keep their parity."""
+    Bn, _, L = delta.shape
+    D = np.zeros((Bn, k + m, L), dtype=np.uint8)
+    D[:, :k] = delta * cols[:, :, None]
+    oracle.rs_encode(k, m, D)
+    out = parity.copy()
+    hit = cols.any(axis=1)
+    out[hit] = parity[hit] ^ D[hit, k:]
+    return out

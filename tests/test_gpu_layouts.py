@@ -13,7 +13,7 @@ kernel that lets the bytes of a partial tail chunk past L leak into its output f
 import numpy as np
 import pytest
 
-from arena import CANARY, GUARD, Region, canary_image, check_arena, codec, place, rup16, torch  # noqa: F401
+from arena import CANARY, GUARD, Region, canary_image, check_arena, codec, place, recover_statuses, rup16, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -177,8 +177,7 @@ def run_rs_step(codec, fec, torch, c, layout, k, m, L, step, masks=None):
         check_arena(dev.cpu().numpy(), model, "in-place reconstruct")
         return
     omodel = oarena.copy()
-    st_want = np.where(e_d == 0, 0, np.where(few, fec.FEC_ERR_TOO_FEW_SHARDS,
-                                             np.where(e_d > slots, fec.FEC_ERR_INVALID_ARG, e_d)))
+    st_want = recover_statuses(fec, e_d, few, slots)
     assert (st_want > 0).any()
     for b in np.flatnonzero(st_want > 0):
         for r, i in enumerate(np.flatnonzero(lost_d[b])):

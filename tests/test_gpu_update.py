@@ -17,7 +17,7 @@ loads); shards of 497 bytes and more put at most 3 blocks into a wave (masks by 
 import numpy as np
 import pytest
 
-from arena import CANARY, Region, canary_image, check_arena, codec, place, rup16, torch  # noqa: F401
+from arena import CANARY, Region, canary_image, check_arena, codec, folded_parity, place, rup16, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -77,15 +77,11 @@ class Batch:
         out = (self.img if img is None else img).copy()
         if m == 0:
             return out
-        hit = cols.any(axis=1)
-        D = np.zeros((B, k + m, L), dtype=np.uint8)
         d = self.new.view(out, 0, L) ^ self.old.view(out, 0, L) if has_old else self.old.view(out, 0, L)
-        D[:, :k] = d * cols[:, :, None]
-        self.oracle.rs_encode(k, m, D)
         p = self.par.view(out, 0, L)
-        p[hit] = p[hit] ^ D[hit, k:]
+        p[...] = folded_parity(self.oracle, k, m, d, cols, p)
         pad = self.par.view(out, L, rup16(L))
-        pad[hit] = 0
+        pad[cols.any(axis=1)] = 0
         return out
 
     def run(self, dev, call, words):
