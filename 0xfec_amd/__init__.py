@@ -90,6 +90,8 @@ lib.fec_rs_locate_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _
 lib.fec_rs_locate_multi_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i, _vp, _vp, _sz, _vp, _i]
 lib.fec_rs_locate_partial_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp, _vp, _i]
 lib.fec_rs_reconstruct_some_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
+lib.fec_rs_reconstruct_some_wide_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp,
+                                                   _i]
 lib.fec_rs_update_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
 lib.fec_rs_encode_idx_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i]
 lib.fec_xor_encode_batch.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
@@ -488,7 +490,8 @@ class Codec:
     # ---- locate (FEC_DEVICE only; device tensors): bad_shard is an int32 device tensor [B] that
     # receives FEC_LOCATE_CLEAN, the corrupt shard's index, or FEC_LOCATE_UNKNOWN per block;
     # present_out an optional 4-byte integer device tensor [B, W], FEC_MASK_WORDS(k + m) <= W <= 8, that
-    # receives the present masks which heal the located blocks (W = 1: rs_reconstruct_some's masks);
+    # receives the present masks which heal the located blocks (W = 1 and k + m <= 32: rs_reconstruct_some's
+    # masks, else rs_reconstruct_some_wide's);
     # counts an optional 4-byte integer device tensor of two elements (located, unknown).
     def rs_locate_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, bad_shard, present_out=None,
                       mask_words=None, counts=None, flags=FEC_DEVICE):
@@ -579,6 +582,31 @@ class Codec:
 
     def rs_reconstruct_some_split(self, k, m, data, parity, masks, want=None, status=None, shard_len=None):
         return self._reconstruct_some(k, m, _Layout(k, m, data, parity, _SOME), masks, want, status, shard_len)
+
+    # ---- wide reconstruct-some (include/fec_hip_some_wide.h; FEC_DEVICE only; k + m <= 256): masks and want
+    # (optional; None = every shard) are 4-byte integer device tensors [B, W] of one shape,
+    # FEC_MASK_WORDS(k + m) <= W <= 8 (wide_masks() builds them); the masks the locate calls write into
+    # present_out are the masks to pass. The raw mirror returns the C return code.
+    def rs_reconstruct_some_wide_raw(self, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss, masks, mask_words,
+                                     want=None, status=None, flags=FEC_DEVICE):
+        return lib.fec_rs_reconstruct_some_wide_batch(self._h, k, m, shard_len, nblocks, data, dbs, parity, pbs, ss,
+                                                      masks, want, mask_words, status, flags)
+
+    def _reconstruct_some_wide(self, k, m, lay, masks, want, status, shard_len):
+        ma, W = self._col_masks(masks, lay.B)
+        wa = None
+        if want is not None:
+            wa, Ww = self._col_masks(want, lay.B)
+            assert Ww == W, "want has the masks' shape"
+        sa = None if status is None else self._words_addr(status, lay.B, "status")
+        return _check(self.rs_reconstruct_some_wide_raw(k, m, *lay.args(shard_len), ma, W, wa, sa),
+                      "fec_rs_reconstruct_some_wide_batch")
+
+    def rs_reconstruct_some_wide(self, k, m, shards, masks, want=None, status=None, shard_len=None):
+        return self._reconstruct_some_wide(k, m, _Layout(k, m, shards, None, _SOME), masks, want, status, shard_len)
+
+    def rs_reconstruct_some_wide_split(self, k, m, data, parity, masks, want=None, status=None, shard_len=None):
+        return self._reconstruct_some_wide(k, m, _Layout(k, m, data, parity, _SOME), masks, want, status, shard_len)
 
     # ---- update and encode-idx (klauspost Update / EncodeIdx; FEC_DEVICE only; device tensors): parity
     # is changed in place by the columns each block's mask names. masks is a 4-byte integer device

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <functional>
 
+#include "../../include/fec_hip_some_wide.h"
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
 #include "fec_locate.hpp"
@@ -616,6 +617,29 @@ int fec_rs_reconstruct_some_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
     return rs_reconstruct_some_device(ctx, k, m, c.s, {present_mask, 1, block_status, ctx->d_err}, want_mask);
+}
+
+// Wide reconstruct-some (fec_hip_some_wide.h): one mask word and a narrow code is the narrow call, as
+// for the two wide decode calls.
+int fec_rs_reconstruct_some_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nblocks, uint8_t* data,
+                                       size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
+                                       size_t shard_stride, const uint32_t* present_mask, const uint32_t* want_mask,
+                                       size_t mask_words, int32_t* block_status, int flags) {
+    if (k + m <= FEC_MAX_DECODE_SHARDS && mask_words == 1)
+        return fec_rs_reconstruct_some_batch(ctx, k, m, shard_len, nblocks, data, data_block_stride, parity,
+                                             parity_block_stride, shard_stride, present_mask, want_mask,
+                                             block_status, flags);
+    Call c{k, m, FEC_MAX_WIDE_SHARDS, false, flags,
+           shards(shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
+    c.null_arg = !present_mask;
+    c.wide = true, c.mask_words = mask_words;
+    c.words[0] = {present_mask, block_status};
+    c.words[1] = {want_mask, nullptr};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_reconstruct_some_wide_device(ctx, k, m, c.s, {present_mask, mask_words, block_status, ctx->d_err},
+                                           want_mask);
 }
 
 // ---------------------------------------------------------------- locate

@@ -255,29 +255,41 @@ static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, const Shard
     });
 }
 
+// The wide plan kernel (fec_wide.hip rs_plan_wide_kernel) for one launch slice of nb blocks from
+// block b0: records of `rows` rows into the stream's workspace. some: the reconstruct-some form, with
+// want masks (null: every shard) strided like the present masks; else the reconstruct / recover
+// form with max_out output slots (0: in place).
+static hipError_t plan_wide_slice(fec_ctx* ctx, uint32_t k, uint32_t m, uint32_t rows, const DecodeWords& words,
+                                  const uint32_t* want, uint32_t max_out, bool some, size_t b0, size_t nb,
+                                  const fk::WideLayout& lay) {
+    const DecodeWords w = words.blocks(b0);
+    fk::WidePlanArgs p{};
+    p.masks = w.masks;
+    p.mask_words = (uint32_t)w.mask_words;
+    p.want = want ? want + b0 * w.mask_words : nullptr;
+    p.plans = ctx->work->d_plans;
+    p.status = w.status;
+    p.err = w.err;
+    p.k = k;
+    p.n = k + m;
+    p.nblocks = (uint32_t)nb;
+    p.rows = rows;
+    p.max_out = max_out;
+    p.lay = lay;
+    p.div_k = fk::make_fastdiv(k);
+    return fk::launch_rs_plan_wide(p, some, ctx->stream);
+}
+
 // Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
 // up to 256 shards.
 int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, const ReconCall& c) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
     uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
     if (c.out.base) rows = std::min(rows, c.out.slots);
+    const uint32_t max_out = c.out.base ? c.out.slots : 0;
     return rs_rebuild_tiles(ctx, k, rows, c.s, c.out, false,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
-                                const DecodeWords w = c.w.blocks(b0);
-                                fk::WidePlanArgs p{};
-                                p.masks = w.masks;
-                                p.mask_words = (uint32_t)w.mask_words;
-                                p.plans = ctx->work->d_plans;
-                                p.status = w.status;
-                                p.err = w.err;
-                                p.k = k;
-                                p.n = k + m;
-                                p.nblocks = (uint32_t)nb;
-                                p.rows = rows;
-                                p.max_out = c.out.base ? c.out.slots : 0;
-                                p.lay = lay;
-                                p.div_k = fk::make_fastdiv(k);
-                                return fk::launch_rs_plan_wide(p, ctx->stream);
+                                return plan_wide_slice(ctx, k, m, rows, c.w, nullptr, max_out, false, b0, nb, lay);
                             });
 }
 
@@ -566,6 +578,18 @@ int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, co
                                 p.nblocks = (uint32_t)nb;
                                 p.lay = lay;
                                 return fk::launch_rs_plan_some(p, ctx->stream);
+                            });
+}
+
+// Wide reconstruct-some (k + m <= 256, masks of mask_words words): the same, with records from the
+// wide plan kernel in its reconstruct-some form.
+int rs_reconstruct_some_wide_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
+                                    const uint32_t* want) {
+    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    const uint32_t rows = fk::some_rows(m);
+    return rs_rebuild_tiles(ctx, k, rows, s, {}, true,
+                            [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
+                                return plan_wide_slice(ctx, k, m, rows, words, want, 0, true, b0, nb, lay);
                             });
 }
 

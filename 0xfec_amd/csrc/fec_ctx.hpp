@@ -244,6 +244,9 @@ struct LocatePartialCall {
 int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartialCall& c);
 int rs_reconstruct_some_device(fec_ctx* ctx, int k, int m, const Shards& s, const DecodeWords& w,
                                const uint32_t* want);
+// want: w.mask_words words per block, as the present masks
+int rs_reconstruct_some_wide_device(fec_ctx* ctx, int k, int m, const Shards& s, const DecodeWords& w,
+                                    const uint32_t* want);
 int rs_encode_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,
                             int* err);
 int xor_encode_device(fec_ctx* ctx, int k, const Shards& s);

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <vector>
 
 #include "../../include/fec_hip.h"
@@ -179,6 +180,120 @@ int fec__selftest_some_plan(void) {
                 rec2[lay.nout_off])
                 return fail;
             if (fk::some_plan_record(rec2.data(), lay, few, few, k, n, ex768, lg) != 0 || rec2[lay.nout_off]) return fail;
+        }
+    }
+    return 0;
+}
+
+// Internal self-test (not part of the public ABI, no device needed): fec__selftest_some_plan for the
+// multi-word records of some_wide_plan_record (fec_some.hpp; wide_logsum / wide_coef are what
+// rs_plan_wide_kernel<true> runs), masks of 8 words. Per code 64 masks: all parity lost; exactly k
+// present, all of them parity (m >= k); shards 31, 32, 63 and 64 lost (those the code has, at most m);
+// the rest seeded losses of 0..m shards. Checked as there: inputs, outputs and every row against
+// M[O[r]] * inverse(rows S of M) with want = NULL, a seeded want subset, a want mask naming nothing
+// missing, and k - 1 present; stray bits at and above n are set in both masks throughout. 0 on
+// success, else 1000 * (code index + 1) + mask index + 1.
+int fec__selftest_some_wide_plan(void) {
+    static const int shapes[][2] = {{20, 13}, {33, 32}, {64, 16}, {16, 240}, {128, 128}, {1, 255}, {255, 1}};
+    constexpr uint32_t W = fk::kWideMaskWords;
+    using Mask = std::array<uint32_t, W>;
+    uint8_t ex768[768];
+    for (uint32_t i = 0; i < 768; ++i) ex768[i] = fk::wide_exp768(i);
+    const uint8_t* lg = gf::kTables.log;
+    uint64_t seed = 0xA0761D6478BD642Full;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    auto get = [](const Mask& w, uint32_t i) { return (w[i >> 5] >> (i & 31u)) & 1u; };
+    auto put = [](Mask& w, uint32_t i, bool v) {
+        w[i >> 5] = (w[i >> 5] & ~(1u << (i & 31u))) | ((uint32_t)v << (i & 31u));
+    };
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix((int)k, (int)n);
+        if (M.empty()) return 1000 * si;
+        const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
+        if (lay.coef_off > fk::kWideHdrMax) return 1000 * si;
+        // bits [0, n) of `bits`, every bit from n on set
+        auto with_stray = [&](const Mask& bits) {
+            Mask w = bits;
+            for (uint32_t i = n; i < 32 * W; ++i) put(w, i, true);
+            return w;
+        };
+        std::vector<uint8_t> rec(lay.stride), rec2(lay.stride);
+        for (int ci = 0; ci < 64; ++ci) {
+            const int fail = 1000 * si + ci + 1;
+            Mask pres{};
+            for (uint32_t i = 0; i < n; ++i) put(pres, i, true);
+            if (ci == 0) {
+                for (uint32_t i = k; i < n; ++i) put(pres, i, false);          // all parity lost
+            } else if (ci == 1 && m >= k) {
+                for (uint32_t i = 0; i < n; ++i) put(pres, i, i >= k && i < 2 * k);   // k present, all parity
+            } else if (ci == 2) {
+                uint32_t lose = m;
+                for (uint32_t i : {31u, 32u, 63u, 64u})
+                    if (i < n && lose) put(pres, i, false), --lose;
+            } else {
+                for (uint32_t lose = rnd() % (m + 1); lose > 0;) {
+                    const uint32_t i = rnd() % n;
+                    if (get(pres, i)) put(pres, i, false), --lose;
+                }
+            }
+            std::vector<uint8_t> S, O;
+            for (uint32_t i = 0; i < n && S.size() < k; ++i)
+                if (get(pres, i)) S.push_back((uint8_t)i);
+            for (uint32_t i = 0; i < n; ++i)
+                if (!get(pres, i)) O.push_back((uint8_t)i);
+            std::fill(rec.begin(), rec.end(), 0xEE);
+            if (fk::some_wide_plan_record(rec.data(), lay, with_stray(pres).data(), nullptr, k, n, ex768, lg) != 0)
+                return fail;
+            if (rec[lay.nout_off] != O.size()) return fail;
+            if (O.empty()) continue;
+            if (memcmp(&rec[lay.in_off], S.data(), k) || memcmp(&rec[lay.out_off], O.data(), O.size())) return fail;
+            std::vector<uint8_t> inv((size_t)k * k);
+            for (uint32_t p = 0; p < k; ++p) memcpy(&inv[(size_t)p * k], &M[(size_t)S[p] * k], k);
+            if (!rs::invert((int)k, inv.data())) return fail;
+            for (size_t r = 0; r < O.size(); ++r)
+                for (uint32_t p = 0; p < k; ++p) {
+                    uint8_t c = 0;   // (M[o] * inv)[p]
+                    for (uint32_t t = 0; t < k; ++t) c ^= gf::mul(M[(size_t)O[r] * k + t], inv[(size_t)t * k + p]);
+                    if (rec[lay.coef_off + r * k + p] != c) return fail;
+                }
+            // a want mask: only the wanted missing shards, each with the row it had
+            Mask want{};
+            for (uint32_t& w : want) w = rnd();
+            const Mask want_s = with_stray(want);
+            std::fill(rec2.begin(), rec2.end(), 0xEE);
+            if (fk::some_wide_plan_record(rec2.data(), lay, pres.data(), want_s.data(), k, n, ex768, lg) != 0)
+                return fail;
+            uint32_t r2 = 0;
+            for (size_t r = 0; r < O.size(); ++r) {
+                if (!get(want, O[r])) continue;
+                if (rec2[lay.out_off + r2] != O[r] ||
+                    memcmp(&rec2[lay.coef_off + r2 * k], &rec[lay.coef_off + r * k], k))
+                    return fail;
+                ++r2;
+            }
+            if (rec2[lay.nout_off] != r2) return fail;
+            if (fk::some_wide_plan_record(rec2.data(), lay, pres.data(), with_stray(pres).data(), k, n, ex768, lg) !=
+                    0 ||
+                rec2[lay.nout_off])
+                return fail;
+            // k - 1 present: too few exactly when something is to rebuild
+            Mask few{};
+            for (uint32_t p = 0; p + 1 < k; ++p) put(few, S[p], true);
+            if (fk::some_wide_plan_record(rec2.data(), lay, few.data(), nullptr, k, n, ex768, lg) !=
+                    FEC_ERR_TOO_FEW_SHARDS ||
+                rec2[lay.nout_off])
+                return fail;
+            if (fk::some_wide_plan_record(rec2.data(), lay, few.data(), few.data(), k, n, ex768, lg) != 0 ||
+                rec2[lay.nout_off])
+                return fail;
         }
     }
     return 0;

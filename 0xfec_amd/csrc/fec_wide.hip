@@ -1,8 +1,9 @@
 // fec_wide.hip — wide RS decode for gfx950: codes of up to 256 shards (klauspost New(k, m) with
 // k + m <= 256), present masks of 1..8 words per block. rs_plan_wide_kernel turns each block's mask
-// into a record (inputs, erased data shards, e x k coefficient bytes, fec_wide.hpp); the rebuild
-// is the generic encode's inner loop (fec_encode.hip rs_encode_kernel) over gathered inputs with a
-// coefficient matrix per block.
+// into a record (inputs, shards to rebuild, e x k coefficient bytes, fec_wide.hpp): the erased data
+// shards for wide reconstruct / recover, every wanted missing shard, parity included, for wide
+// reconstruct-some. The rebuild is the generic encode's inner loop (fec_encode.hip rs_encode_kernel)
+// over gathered inputs with a coefficient matrix per block.
 #include "fec_recon.hpp"
 #include "fec_wide.hpp"
 
@@ -10,18 +11,24 @@ namespace fk {
 
 // ------------------------------------------------------------------ wide plan
 // One wave per block, four blocks per workgroup. Lanes take shard indices lane, lane + 64, ..:
-// ballots of the present and the erased-data bits give each shard its place in the input list S
-// (the first k present, ascending) and the output list O (erased data, ascending). Lane p then
-// builds D_p and lane r builds N_r (k-long sums over S in LDS), and the wave writes the e * k
-// coefficient bytes, four per lane per store, straight into the record.
+// ballots of the present and the to-rebuild bits give each shard its place in the input list S
+// (the first k present, ascending) and the output list O (ascending). Lane p then builds D_p and
+// lane r builds N_r (k-long sums over S in LDS), and the wave writes the e * k coefficient bytes,
+// four per lane per store, straight into the record.
+// The variable part is which shards go into O. SOME = false (wide reconstruct / recover): the
+// missing data shards; recover (a.max_out set) reports their number and refuses more than its out
+// slots. SOME = true (wide reconstruct-some): the missing shards below n that the block's want mask
+// names (a.want null: every one), data and parity alike; in place, so a.max_out is not looked at.
+// Either way a block that has something to rebuild and fewer than k shards present gets -4.
 constexpr int kWidePlanWaves = kThreads / 64;
 
 struct WidePlanWave {
     uint8_t hdr[kWideHdrMax];   // the record's header: S, O, nout
     uint8_t D[256];
-    uint8_t N[128];
+    uint8_t N[256];             // up to 255 rows (reconstruct-some of RS(1,255))
 };
 
+template <bool SOME>
 __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_exp[768];
     __shared__ __attribute__((aligned(16))) uint8_t s_log[256];
@@ -36,6 +43,8 @@ __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) 
     const WideLayout lay = a.lay;
     const uint32_t k = a.k, n = a.n;
     const uint32_t* mw = a.masks + (uint64_t)b * a.mask_words;
+    const uint32_t* ww = SOME && a.want ? a.want + (uint64_t)b * a.mask_words : nullptr;
+    const uint32_t max_out = SOME ? 0u : a.max_out;
     uint32_t* hdr32 = reinterpret_cast<uint32_t*>(W.hdr);
     const uint32_t hw = lay.coef_off / 4;
     for (uint32_t i = lane; i < hw; i += 64) hdr32[i] = 0;
@@ -46,7 +55,8 @@ __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) 
         const uint32_t idx = base + lane;
         // bits at and above n are ignored; idx < n implies idx / 32 < mask_words (checked by the host)
         const bool pres = idx < n && ((mw[idx >> 5] >> (idx & 31u)) & 1u);
-        const bool lost = idx < k && !pres;
+        bool lost = idx < (SOME ? n : k) && !pres;
+        if (SOME && ww) lost = lost && ((ww[idx >> 5] >> (idx & 31u)) & 1u);
         const uint64_t bp = __ballot(pres), bl = __ballot(lost);
         const uint32_t pp = npres + (uint32_t)__popcll(bp & below);
         const uint32_t pl = e + (uint32_t)__popcll(bl & below);
@@ -56,17 +66,19 @@ __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) 
         e += (uint32_t)__popcll(bl);
     }
     // statuses and the sticky word as rs_plan_kernel (fec_decode.hip)
-    int32_t st = a.max_out ? (int32_t)e : 0;   // recover reports the rebuilt count
+    int32_t st = max_out ? (int32_t)e : 0;   // recover reports the rebuilt count
     uint32_t nout = 0;
     if (e == 0) {
     } else if (npres < k) {
         st = -4;  // FEC_ERR_TOO_FEW_SHARDS
         if (lane == 0) wave_flag(a.err, 1);
-    } else if (a.max_out && e > a.max_out) {
+    } else if (max_out && e > max_out) {
         st = -1;  // FEC_ERR_INVALID_ARG: more erasures than output slots
         if (lane == 0) wave_flag(a.err, 2);
     } else {
-        nout = e;   // <= rows: a recoverable block has e <= min(k, m), and e <= max_out here
+        // <= rows: a recoverable block misses at most m shards, at most min(k, m) of them data, and
+        // e <= max_out here
+        nout = e;
     }
     if (lane == 0) {
         W.hdr[lay.nout_off] = (uint8_t)nout;
@@ -207,10 +219,11 @@ __global__ __launch_bounds__(kThreads) void rs_rebuild_wide_kernel(WideReconArgs
     }
 }
 
-hipError_t launch_rs_plan_wide(const WidePlanArgs& a, hipStream_t s) {
+hipError_t launch_rs_plan_wide(const WidePlanArgs& a, bool some, hipStream_t s) {
     const int grid = (int)((a.nblocks + kWidePlanWaves - 1) / kWidePlanWaves);
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(rs_plan_wide_kernel, dim3(grid), dim3(kThreads), 0, s, a);
+    if (some) hipLaunchKernelGGL(rs_plan_wide_kernel<true>, dim3(grid), dim3(kThreads), 0, s, a);
+    else hipLaunchKernelGGL(rs_plan_wide_kernel<false>, dim3(grid), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -19,8 +19,10 @@ constexpr uint32_t kWideMaxTileBlocks = 14;
 
 // Wide plan record, one of `stride` bytes per block (in block order):
 //   [in_off,   +rup8(k))  the first k present shards, ascending (zero padded)
-//   [out_off,  +rows)     the erased data shards, ascending
-//   [nout_off]            erased data shards to rebuild (0: nothing / failed); <= min(k, m) <= 128
+//   [out_off,  +rows)     the shards to rebuild, ascending: erased data shards (reconstruct-some:
+//                         the wanted missing shards, data and parity)
+//   [nout_off]            shards to rebuild (0: nothing / failed); <= min(k, m) <= 128
+//                         (reconstruct-some: <= m <= 255)
 //   [coef_off, +rows*k)   GF coefficients, row r = output r, column p = input p
 // [0, coef_off) is the record's header: the rebuild stages it in LDS and reads the coefficient
 // bytes straight from the record.
@@ -63,6 +65,7 @@ GF_HD inline uint8_t wide_coef(const uint8_t* ex768, const uint8_t* lg, uint32_t
 struct WidePlanArgs {
     const uint32_t* masks;     // nblocks * mask_words
     uint32_t mask_words;
+    const uint32_t* want;      // reconstruct-some: nblocks * mask_words want words (null: every shard)
     uint8_t* plans;            // nblocks * lay.stride bytes
     int32_t* status;           // optional
     int* err;                  // sticky error word
@@ -105,7 +108,9 @@ inline size_t wide_recon_lds(uint32_t g, uint32_t tk, const WideLayout& lay) {
     return (size_t)g * kWideRowPass * tk * 32 + (size_t)g * lay.coef_off;
 }
 
-hipError_t launch_rs_plan_wide(const WidePlanArgs& a, hipStream_t s);
+// some: the records of wide reconstruct-some (outputs: the wanted missing shards, data and parity;
+// a.rows = some_rows(m), fec_some.hpp), else those of wide reconstruct / recover (a.want unused).
+hipError_t launch_rs_plan_wide(const WidePlanArgs& a, bool some, hipStream_t s);
 // some: the reconstruct-some form of the tile (records of fec_some.hpp; rebuilt shards go to their own
 // slots in the data and the parity region, a.out unused), else the wide reconstruct / recover form.
 hipError_t launch_rs_rebuild_wide(const WideReconArgs& a, bool some, hipStream_t s);

@@ -325,7 +325,7 @@ int fec_rs_verify_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
  *                set, except bit s of a located block; bits at and above k + m zero. With k + m <= 32
  *                and mask_words == 1 it is the present_mask with which fec_rs_reconstruct_some_batch
  *                rebuilds exactly the located shard, data or parity; for wider codes that of
- *                fec_rs_reconstruct_wide_batch (a located parity shard is then re-encoded).
+ *                fec_rs_reconstruct_some_wide_batch (fec_hip_some_wide.h), which does the same.
  *                FEC_MASK_WORDS(k + m) <= mask_words <= 8, else FEC_ERR_INVALID_ARG, whether or not
  *                present_out is given
  *   counts       (optional) two uint32: when the call's work completes on the stream, [0] holds the
@@ -379,8 +379,8 @@ int fec_rs_locate_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
  *                set, less the bits of E_b; an unknown block keeps all k + m bits, so that healing
  *                leaves it untouched; bits at and above k + m zero. These are the masks that heal
  *                through fec_rs_reconstruct_some_batch (k + m <= 32, mask_words == 1) or
- *                fec_rs_reconstruct_wide_batch (which rebuilds data shards: a located parity shard is
- *                then re-encoded). FEC_MASK_WORDS(k + m) <= mask_words <= 8, else
+ *                fec_rs_reconstruct_some_wide_batch (fec_hip_some_wide.h; any k + m), located parity
+ *                shards included. FEC_MASK_WORDS(k + m) <= mask_words <= 8, else
  *                FEC_ERR_INVALID_ARG, whether or not present_out is given
  *   counts       (optional) two uint32: when the call's work completes on the stream, [0] holds the
  *                located blocks (count >= 1) and [1] the unknown ones
@@ -443,8 +443,8 @@ int fec_rs_locate_multi_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size
  *                k + m zero. It may be the same pointer as present_mask (exact aliasing only: the
  *                masks are then updated in place); any other overlap is undefined. These masks go
  *                straight into fec_rs_reconstruct_some_batch (k + m <= 32, mask_words == 1) or
- *                fec_rs_reconstruct_wide_batch, which rebuilds the missing and the located shards in
- *                one go (the wide call: the data shards among them; parity is then re-encoded):
+ *                fec_rs_reconstruct_some_wide_batch (fec_hip_some_wide.h; any k + m), which rebuilds
+ *                the missing and the located shards, data and parity, in one go:
  *                e_b + |E_b| <= m leaves k shards present
  *   counts       (optional) three uint32: when the call's work completes on the stream, [0] holds the
  *                located blocks, [1] the unknown ones, [2] those with too few shards
