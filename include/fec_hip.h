@@ -369,7 +369,8 @@ int fec_rs_locate_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size_t nbl
  *   FEC_LOCATE_UNKNOWN  otherwise; with m <= 1 (T = 0) every inconsistent block
  * With m == 0 every block is 0. t corrupt shards with t <= T are always located exactly; with
  * T < t <= m - T the block is always unknown; with t > m - T a wrong set can be named, as by any
- * decoder past its distance. With max_bad == 1 the results agree with fec_rs_locate_batch block for
+ * decoder past its distance: the result is always the smallest explaining set of at most T shards if
+ * one exists, which past the radius need not be the shards that were changed. With max_bad == 1 the results agree with fec_rs_locate_batch block for
  * block: clean with 0, shard s with count 1 and bit s cleared, unknown with unknown.
  *
  * Outputs, all device memory, 4-byte aligned (else FEC_ERR_ALIGNMENT); the call sets every word of
@@ -430,7 +431,9 @@ int fec_rs_locate_multi_batch(fec_ctx *ctx, int k, int m, size_t shard_len, size
  *   FEC_LOCATE_UNKNOWN   the present shards are inconsistent and no such set exists; with T_b == 0
  *                        every inconsistent block
  * t corrupt present shards with t <= T_b are always located exactly; with T_b < t <= (m - e_b) - T_b the
- * block is always unknown; beyond that a wrong set can be named. max_bad lies in [0,
+ * block is always unknown; beyond that a wrong set can be named: the result is always the smallest
+ * explaining set of at most T_b present shards if one exists, which past the radius need not be the
+ * shards that were changed. max_bad lies in [0,
  * FEC_LOCATE_MAX_BAD]; 0 makes the call a verify of blocks with missing shards (results 0, unknown or
  * too few). With every mask full and max_bad >= 1 the results, masks and counts[0..1] are those of
  * fec_rs_locate_multi_batch block for block, and counts[2] is 0.

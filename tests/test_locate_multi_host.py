@@ -46,7 +46,9 @@ def test_solver_and_merge_equal_the_definition(fec):
     # (1,2), (2,2), (6,3), (3,5), (8,4), (1,8), (16,8), (20,10), (4,16), (240,16), (31,1), (32,0), max_bad
     # 1 .. 8, 42 seeded blocks each in fourteen error patterns: every subset of at most T shards tried
     # where they can be counted, the two guarantees everywhere, max_bad = 1 against locate_chunk /
-    # locate_merge
+    # locate_merge. (Subsets are counted for n <= 12, and (16,8) at max_bad <= 2; codes of n > 12 are
+    # checked against the definition, past the radius too, by test_locate_hard_cases.py's port of the
+    # column solver and by test_gpu_locate_hard.py on the device.)
     lib = ctypes.CDLL(fec._LIB_PATH)
     assert lib.fec__selftest_locate_multi() == 0
 
