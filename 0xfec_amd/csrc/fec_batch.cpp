@@ -1,5 +1,8 @@
-// fec_batch.cpp — RepairQueue (repair_queue.go restated) and BatchEncoder (deferred, batched
-// repair-symbol generation on the GPU). Design and contracts: include/fec_batch.hpp.
+// fec_batch.cpp — the batching layer a sender or receiver drives: RepairQueue (repair_queue.go
+// restated), RecoveredQueue, PacketPool (registered packet buffers the device gathers from), and
+// the two coders, BatchEncoder (deferred, batched repair-symbol generation) and BatchDecoder
+// (deferred, batched recovery), over one staging pipeline: sets that own their buffers, one input
+// step per flush, one walk over the sets in flight. Design and contracts: include/fec_batch.hpp.
 #include "../../include/fec_batch.hpp"
 
 #include <hip/hip_runtime.h>
@@ -52,7 +55,7 @@ bool RepairQueue::Closed() {
     return closed_;
 }
 
-// ------------------------------------------------------------------ BatchEncoder
+// ------------------------------------------------------------------ shared by both coders
 
 namespace {
 constexpr size_t kSlotMax = (kMaxFECPacketBufferSize + kRepairPayloadMetadataLen + 15) & ~size_t(15);   // 1440
@@ -127,6 +130,126 @@ uint64_t PacketPool::Lookup(const uint8_t* p, size_t len, std::shared_ptr<Packet
     return 0;
 }
 
+// ------------------------------------------------------------------ staging sets
+
+StageBuf::~StageBuf() {
+    if (host) (void)hipHostFree(host);
+    if (dev) (void)hipFree(dev);
+}
+
+Error StageBuf::alloc(size_t bytes, const char* what) {
+    StageBuf b;   // frees what it got so far when a later step fails
+    hipError_t h;
+    if ((h = hipHostMalloc(&b.host, bytes, hipHostMallocDefault)) != hipSuccess)
+        return hip_error(h, what ? what : "hipHostMalloc");
+    if ((h = hipMalloc(&b.dev, bytes)) != hipSuccess) return hip_error(h, what ? what : "hipMalloc");
+    if ((h = hipHostGetDevicePointer(&b.mapped, b.host, 0)) != hipSuccess) return hip_error(h, "hipHostGetDevicePointer");
+    *this = std::move(b);   // what this held before goes with b
+    return Error::nil();
+}
+
+StageEvent::~StageEvent() {
+    if (ev) (void)hipEventDestroy((hipEvent_t)ev);
+}
+
+Error StageSet::alloc(size_t in_bytes, size_t out_bytes, size_t desc_bytes, const char* what) {
+    Error e;
+    if ((e = in.alloc(in_bytes, what)).ok() && (e = out.alloc(out_bytes, what)).ok() &&
+        (e = desc.alloc(desc_bytes, what)).ok()) {
+        hipEvent_t ev;
+        const hipError_t h = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (h == hipSuccess) {
+            StageEvent fresh;
+            fresh.ev = ev;
+            done = std::move(fresh);
+            return e;
+        }
+        e = hip_error(h, "hipEventCreate");
+    }
+    in = StageBuf();
+    out = StageBuf();
+    desc = StageBuf();
+    return e;
+}
+
+namespace {
+// The rs / xor pair of a coder for (scheme, k, m).
+Error make_scheme(DecoderFECScheme scheme, int k, int m, const std::shared_ptr<Engine>& engine,
+                  std::unique_ptr<ReedSolomonScheme>* rs, std::unique_ptr<XorScheme>* x) {
+    if (scheme == ReedSolomonFECScheme) return ReedSolomonScheme::New(k, m, engine, rs);
+    if (scheme != XORFECScheme) return Error::text("no FEC scheme");
+    if (m != 1) return Error::text("xor only supports 1 repair symbol");
+    if (k < 1 || k > 255) return Error::text("invalid number of source symbols");
+    x->reset(new XorScheme(engine));
+    return Error::nil();
+}
+
+Error wait_set(const StageSet& s) {
+    const hipError_t h = hipEventSynchronize((hipEvent_t)s.done.ev);
+    return h == hipSuccess ? Error::nil() : hip_error(h, "hipEventSynchronize");
+}
+
+// The input step of a flush of B blocks of `shards` shards each; *in = the device address the code
+// reads them at. A small set is coded straight from and into its pinned buffers (*zc): one launch
+// (two when gathered) and an event, where the copy form makes copies around the kernels, each a
+// call of its own and a copy-engine round trip (knob bat_zc: input bytes up to which;
+// go_batch_bench burst). A set holding references is gathered by the device as a whole.
+Error flush_input(StageSet& s, size_t B, size_t shards, int device, hipStream_t st, bool* zc, uint8_t** in) {
+    const size_t count = B * shards;
+    hipError_t h;
+    *zc = count * s.slot <= (size_t)std::max(0, (int)fk::g_tune.bat_zc);
+    *in = static_cast<uint8_t*>(*zc ? s.in.mapped : s.in.dev);
+    if (s.gather) {
+        const void* desc = s.desc.mapped;
+        if (!*zc) {
+            if ((h = hipMemcpyAsync(s.desc.dev, s.desc.host, count * sizeof(fk::GatherDesc), hipMemcpyHostToDevice, st)) !=
+                hipSuccess)
+                return hip_error(h, "hipMemcpyAsync H2D");
+            desc = s.desc.dev;
+        }
+        if ((h = hipSetDevice(device)) != hipSuccess) return hip_error(h, "hipSetDevice");
+        *in = static_cast<uint8_t*>(s.in.dev);
+        if ((h = fk::launch_gather_desc(static_cast<const fk::GatherDesc*>(desc), (uint32_t)count, *in, s.slot, st)) !=
+            hipSuccess)
+            return hip_error(h, "gather launch");
+    } else if (!*zc && (h = hipMemcpyAsync(s.in.dev, s.in.host, count * s.slot, hipMemcpyHostToDevice, st)) != hipSuccess) {
+        return hip_error(h, "hipMemcpyAsync H2D");
+    }
+    return Error::nil();
+}
+
+// A set's batch is queued on st: record its event, mark it in flight, make the other set the one
+// being staged.
+Error launched(StageSet& s, hipStream_t st, int* cur) {
+    const hipError_t h = hipEventRecord((hipEvent_t)s.done.ev, st);
+    if (h != hipSuccess) return hip_error(h, "hipEventRecord");
+    s.inFlight = true;
+    *cur ^= 1;
+    return Error::nil();
+}
+
+// done(set) for the sets in flight, older first (the older batch is the one not being staged):
+// poll: those whose event has completed, stopping at the first that has not (later batches complete
+// later: one stream); else each after waiting for it.
+template <class Set, class Done>
+Error visit_in_flight(Set (&sets)[2], int cur, bool poll, Done&& done) {
+    for (int i = 1; i >= 0; --i) {
+        Set& s = sets[cur ^ i];
+        if (!s.inFlight) continue;
+        Error e;
+        if (poll) {
+            const hipError_t h = hipEventQuery((hipEvent_t)s.done.ev);
+            if (h == hipErrorNotReady) break;
+            if (h != hipSuccess) return hip_error(h, "hipEventQuery");
+        } else if (!(e = wait_set(s)).ok()) {
+            return e;
+        }
+        if (!(e = done(s)).ok()) return e;
+    }
+    return Error::nil();
+}
+}  // namespace
+
 // ------------------------------------------------------------------ BatchEncoder
 
 Error BatchEncoder::New(DecoderFECScheme scheme, int k, int m, size_t maxBlocks, std::shared_ptr<Engine> engine,
@@ -134,60 +257,28 @@ Error BatchEncoder::New(DecoderFECScheme scheme, int k, int m, size_t maxBlocks,
     out->reset();
     if (maxBlocks == 0) return Error::text("batch must hold at least one block");
     std::unique_ptr<BatchEncoder> e(new BatchEncoder(scheme, k, m, maxBlocks, std::move(engine)));
-    if (scheme == ReedSolomonFECScheme) {
-        Error err = ReedSolomonScheme::New(k, m, e->engine_, &e->rs_);
-        if (!err.ok()) return err;
-    } else if (scheme == XORFECScheme) {
-        if (m != 1) return Error::text("xor only supports 1 repair symbol");
-        if (k < 1 || k > 255) return Error::text("invalid number of source symbols");
-        e->xor_.reset(new XorScheme(e->engine_));
-    } else {
-        return Error::text("no FEC scheme");
-    }
+    Error err = make_scheme(scheme, k, m, e->engine_, &e->rs_, &e->xor_);
+    if (!err.ok()) return err;
     *out = std::move(e);
     return Error::nil();
 }
 
 BatchEncoder::~BatchEncoder() {
-    for (Set& s : sets_) {
-        if (s.inFlight && s.done) (void)hipEventSynchronize((hipEvent_t)s.done);
-        if (s.done) (void)hipEventDestroy((hipEvent_t)s.done);
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_out) (void)hipFree(s.d_out);
-        if (s.h_desc) (void)hipHostFree(s.h_desc);
-        if (s.d_desc) (void)hipFree(s.d_desc);
-    }
+    for (Set& s : sets_)   // a set still in flight completes before its buffers go
+        if (s.inFlight) (void)wait_set(s);
 }
 
 Error BatchEncoder::init() {
     fec_ctx* ctx = nullptr;
     Error e = engine_->ctx(&ctx);
     if (!e.ok()) return e;
-    const size_t in_bytes = maxBlocks_ * (size_t)k_ * kSlotMax;
-    const size_t out_bytes = maxBlocks_ * (size_t)m_ * kSlotMax;
+    const size_t shards = maxBlocks_ * (size_t)k_;
     for (Set& s : sets_) {
-        hipError_t h;
-        if ((h = hipHostMalloc(&s.h_in, in_bytes, hipHostMallocDefault)) != hipSuccess) return hip_error(h, "hipHostMalloc");
-        if ((h = hipHostMalloc(&s.h_out, out_bytes, hipHostMallocDefault)) != hipSuccess) return hip_error(h, "hipHostMalloc");
-        if ((h = hipMalloc(&s.d_in, in_bytes)) != hipSuccess) return hip_error(h, "hipMalloc");
-        if ((h = hipMalloc(&s.d_out, out_bytes)) != hipSuccess) return hip_error(h, "hipMalloc");
-        const size_t desc_bytes = maxBlocks_ * (size_t)k_ * sizeof(fk::GatherDesc);
-        if ((h = hipHostMalloc(&s.h_desc, desc_bytes, hipHostMallocDefault)) != hipSuccess)
-            return hip_error(h, "hipHostMalloc");
-        if ((h = hipMalloc(&s.d_desc, desc_bytes)) != hipSuccess) return hip_error(h, "hipMalloc");
-        void *in_dev = nullptr, *out_dev = nullptr, *desc_dev = nullptr;
-        if ((h = hipHostGetDevicePointer(&in_dev, s.h_in, 0)) != hipSuccess ||
-            (h = hipHostGetDevicePointer(&out_dev, s.h_out, 0)) != hipSuccess ||
-            (h = hipHostGetDevicePointer(&desc_dev, s.h_desc, 0)) != hipSuccess)
-            return hip_error(h, "hipHostGetDevicePointer");
-        s.in_dev = (uint64_t)(uintptr_t)in_dev;
-        s.out_dev = static_cast<uint8_t*>(out_dev);
-        s.desc_dev = desc_dev;
-        hipEvent_t ev;
-        if ((h = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return hip_error(h, "hipEventCreate");
-        s.done = ev;
+        e = s.alloc(shards * kSlotMax, maxBlocks_ * (size_t)m_ * kSlotMax, shards * sizeof(fk::GatherDesc));
+        if (!e.ok()) {
+            for (Set& t : sets_) t = Set();   // nothing is staged yet: both sets back to empty
+            return e;
+        }
     }
     ready_ = true;
     return Error::nil();
@@ -195,32 +286,30 @@ Error BatchEncoder::init() {
 
 Error BatchEncoder::Submit(Block& b, RepairQueue* q) {
     if (!q) return Error::text("nil repair queue");
+    auto stage = [&](uint8_t* dst, size_t stride, size_t* L) {
+        int count = k_;
+        Error e = rs_ ? rs_->stageRepairInput(b, dst, stride, L) : xor_->stageRepairInput(b, dst, stride, L, &count);
+        if (e.ok() && count != k_) e = Error::text("block does not match the encoder's source symbol count");
+        return e;
+    };
     // Validate first (the reference's errors take precedence over any device work), staging
     // into a host scratch slot until the pinned sets exist.
     const size_t want = round16(kRepairPayloadMetadataLen + (size_t)std::max(0, b.biggestSourceSymbolLenSoFar));
+    size_t L = 0;
     if (!ready_) {
         std::vector<uint8_t> scratch((size_t)std::max(k_, 1) * kSlotMax);
-        size_t L = 0;
-        int count = 0;
-        Error e = rs_ ? rs_->stageRepairInput(b, scratch.data(), kSlotMax, &L)
-                      : xor_->stageRepairInput(b, scratch.data(), kSlotMax, &L, &count);
+        Error e = stage(scratch.data(), kSlotMax, &L);
         if (!e.ok()) return e;
-        if (xor_ && count != k_) return Error::text("block does not match the encoder's source symbol count");
     }
     Set* s = nullptr;
     Error e = slotFor(want, &s);
     if (!e.ok()) return e;
-    uint8_t* dst = s->h_in + s->blocks.size() * (size_t)k_ * s->slot;
-    size_t L = 0;
-    int count = 0;
-    e = rs_ ? rs_->stageRepairInput(b, dst, s->slot, &L) : xor_->stageRepairInput(b, dst, s->slot, &L, &count);
-    if (!e.ok()) return e;
-    if (xor_ && count != k_) return Error::text("block does not match the encoder's source symbol count");
+    const size_t at = s->blocks.size() * (size_t)k_;
+    if (!(e = stage(s->in.h<uint8_t>() + at * s->slot, s->slot, &L)).ok()) return e;
     // the framed shards as gather descriptors too, in case a referenced block joins this batch
-    fk::GatherDesc* desc = static_cast<fk::GatherDesc*>(s->h_desc) + s->blocks.size() * (size_t)k_;
-    for (int i = 0; i < k_; ++i)
-        desc[i] = fk::GatherDesc{s->in_dev + (uint64_t)(dst - s->h_in) + (uint64_t)i * s->slot, (uint32_t)L, fk::kNoFrame};
-    s->blocks.push_back(Pending{q, q ? q->token() : nullptr, b.id, L});
+    fk::GatherDesc* desc = s->desc.h<fk::GatherDesc>() + at;
+    for (int i = 0; i < k_; ++i) desc[i] = fk::GatherDesc{s->inDev() + (at + i) * s->slot, (uint32_t)L, fk::kNoFrame};
+    s->blocks.push_back(Pending{q, q->token(), b.id, L});
     s->maxLen = std::max(s->maxLen, L);
     return Error::nil();
 }
@@ -250,6 +339,19 @@ Error BatchEncoder::slotFor(size_t want, Set** out) {
 
 Error BatchEncoder::SubmitPayloads(BlockID id, const uint8_t* const* payloads, const size_t* lens, int count,
                                    RepairQueue* q) {
+    return stageBlock(id, payloads, lens, count, false, q);
+}
+
+Error BatchEncoder::SubmitRefs(BlockID id, const uint8_t* const* payloads, const size_t* lens, int count,
+                               RepairQueue* q) {
+    return stageBlock(id, payloads, lens, count, true, q);
+}
+
+// One block given as its payloads: each either framed into its pinned slot here, or (refs, and it
+// lies in a registered pool) left where it is, to be gathered and framed by the device. Every shard
+// gets a gather descriptor, so a batch is gathered as a whole once any shard needs it.
+Error BatchEncoder::stageBlock(BlockID id, const uint8_t* const* payloads, const size_t* lens, int count, bool refs,
+                               RepairQueue* q) {
     if (count < 0 || (count && (!payloads || !lens))) return Error::text("invalid payload list");
     // repairSymbols' checks for a block holding exactly these payloads: complete (reed_solomon.go:27,
     // xor.go:15) -> (XOR: one repair symbol) -> size (reed_solomon.go:31, xor.go:23)
@@ -257,33 +359,12 @@ Error BatchEncoder::SubmitPayloads(BlockID id, const uint8_t* const* payloads, c
     size_t biggest = 0;
     for (int i = 0; i < count; ++i) biggest = std::max(biggest, lens[i]);
     if (biggest > kMaxFECPacketBufferSize) return errTooBig((int)biggest);
-    Set* s = nullptr;
-    Error e = slotFor(round16(biggest + kRepairPayloadMetadataLen), &s);
-    if (!e.ok()) return e;
-    return stageBlock(s, id, payloads, lens, biggest, false, q);
-}
-
-Error BatchEncoder::SubmitRefs(BlockID id, const uint8_t* const* payloads, const size_t* lens, int count,
-                               RepairQueue* q) {
-    if (count < 0 || (count && (!payloads || !lens))) return Error::text("invalid payload list");
-    if (count != k_) return errIncomplete();   // the same checks, in the same order, as SubmitPayloads
-    size_t biggest = 0;
-    for (int i = 0; i < count; ++i) biggest = std::max(biggest, lens[i]);
-    if (biggest > kMaxFECPacketBufferSize) return errTooBig((int)biggest);
-    Set* s = nullptr;
-    Error e = slotFor(round16(biggest + kRepairPayloadMetadataLen), &s);
-    if (!e.ok()) return e;
-    return stageBlock(s, id, payloads, lens, biggest, true, q);
-}
-
-// One validated block into set s: each payload either framed into its pinned slot here, or (refs,
-// and it lies in a registered pool) left where it is, to be gathered and framed by the device.
-// Every shard gets a gather descriptor, so a batch is gathered as a whole once any shard needs it.
-Error BatchEncoder::stageBlock(Set* s, BlockID id, const uint8_t* const* payloads, const size_t* lens, size_t biggest,
-                               bool refs, RepairQueue* q) {
     const size_t L = biggest + kRepairPayloadMetadataLen;
-    uint8_t* dst = s->h_in + s->blocks.size() * (size_t)k_ * s->slot;
-    fk::GatherDesc* desc = static_cast<fk::GatherDesc*>(s->h_desc) + s->blocks.size() * (size_t)k_;
+    Set* s = nullptr;
+    Error e = slotFor(round16(L), &s);
+    if (!e.ok()) return e;
+    const size_t at = s->blocks.size() * (size_t)k_;
+    fk::GatherDesc* desc = s->desc.h<fk::GatherDesc>() + at;
     for (int i = 0; i < k_; ++i) {
         if (refs && lens[i]) {
             // the pools this batch already holds first (no lock, no reference count traffic: the
@@ -301,14 +382,14 @@ Error BatchEncoder::stageBlock(Set* s, BlockID id, const uint8_t* const* payload
                 continue;
             }
         }
-        uint8_t* slot = dst + (size_t)i * s->slot;
+        uint8_t* slot = s->in.h<uint8_t>() + (at + i) * s->slot;
         if (lens[i]) memcpy(slot, payloads[i], lens[i]);
         memset(slot + lens[i], 0, round16(L) - lens[i]);
         // RS: big-endian length trailer at [biggest] (reed_solomon.go:77-87); XOR: the same
         // BE16 XORed in (xor.go:49-53), which for one framed payload is the same bytes
         slot[biggest] = (uint8_t)(lens[i] >> 8);
         slot[biggest + 1] = (uint8_t)(lens[i] & 0xFF);
-        desc[i] = fk::GatherDesc{s->in_dev + (uint64_t)(slot - s->h_in), (uint32_t)L, fk::kNoFrame};
+        desc[i] = fk::GatherDesc{s->inDev() + (at + i) * s->slot, (uint32_t)L, fk::kNoFrame};
     }
     s->blocks.push_back(Pending{q, q ? q->token() : nullptr, id, L});
     s->maxLen = std::max(s->maxLen, L);
@@ -326,7 +407,7 @@ bool BatchEncoder::PeekRaw(RawView* out) {
     if (holding_ < 0) return false;
     const Set& s = sets_[holding_];
     const Pending& p = s.blocks[s.rawNext];
-    *out = RawView{p.id, p.len, s.h_out + s.rawNext * (size_t)m_ * s.slot, s.slot};
+    *out = RawView{p.id, p.len, s.out.h<uint8_t>() + s.rawNext * (size_t)m_ * s.slot, s.slot};
     return true;
 }
 
@@ -337,32 +418,36 @@ void BatchEncoder::PopRaw() {
     }
     if (holding_ < 0) return;
     Set& s = sets_[holding_];
-    if (++s.rawNext < s.blocks.size()) return;
-    s.blocks.clear();
-    s.maxLen = 0;
-    s.rawNext = 0;
-    holding_ = -1;
+    if (++s.rawNext == s.blocks.size()) handBack(s);
 }
 
 size_t BatchEncoder::RawLen() const {
     return raw_.size() + (holding_ >= 0 ? sets_[holding_].blocks.size() - sets_[holding_].rawNext : 0);
 }
 
-void BatchEncoder::spill(Set& s) {
-    for (size_t i = s.rawNext; i < s.blocks.size(); ++i) {
-        const Pending& p = s.blocks[i];
-        RawBlock rb;
-        rb.id = p.id;
-        rb.len = p.len;
-        rb.bytes.resize((size_t)m_ * p.len);
-        for (int j = 0; j < m_; ++j)
-            memcpy(rb.bytes.data() + (size_t)j * p.len, s.h_out + (i * (size_t)m_ + j) * s.slot, p.len);
-        raw_.push_back(std::move(rb));
-    }
+void BatchEncoder::keepRaw(const Set& s, size_t i) {
+    const Pending& p = s.blocks[i];
+    RawBlock rb;
+    rb.id = p.id;
+    rb.len = p.len;
+    rb.bytes.resize((size_t)m_ * p.len);   // the payloads back to back
+    for (int j = 0; j < m_; ++j)
+        memcpy(rb.bytes.data() + (size_t)j * p.len, s.out.h<uint8_t>() + (i * (size_t)m_ + j) * s.slot, p.len);
+    raw_.push_back(std::move(rb));
+}
+
+// No set is in flight and holding at once, and collect() spills any other holding set first, so
+// the set handed back is the holding one or there is none.
+void BatchEncoder::handBack(Set& s) {
     s.blocks.clear();
     s.maxLen = 0;
     s.rawNext = 0;
     holding_ = -1;
+}
+
+void BatchEncoder::spill(Set& s) {
+    for (size_t i = s.rawNext; i < s.blocks.size(); ++i) keepRaw(s, i);
+    handBack(s);
 }
 
 Error BatchEncoder::flushImpl(size_t* delivered) {
@@ -377,30 +462,10 @@ Error BatchEncoder::flushImpl(size_t* delivered) {
     if (!e.ok()) return e;
     hipStream_t st = (hipStream_t)fec_ctx_stream(ctx);
     const size_t B = s.blocks.size();
-    hipError_t h;
-    // a small set is coded straight from and into its pinned buffers: one launch (two when
-    // gathered) and an event instead of a copy up, the launch, a copy down (knob bat_zc, as the
-    // decoder's sets)
-    const bool zc = B * (size_t)k_ * s.slot <= (size_t)std::max(0, (int)fk::g_tune.bat_zc);
-    uint8_t* in = zc ? reinterpret_cast<uint8_t*>((uintptr_t)s.in_dev) : s.d_in;
-    uint8_t* out = zc ? s.out_dev : s.d_out;
-    if (s.gather) {   // referenced payloads: the device pulls every shard of the batch itself
-        const void* desc = s.desc_dev;
-        if (!zc) {
-            if ((h = hipMemcpyAsync(s.d_desc, s.h_desc, B * (size_t)k_ * sizeof(fk::GatherDesc), hipMemcpyHostToDevice,
-                                    st)) != hipSuccess)
-                return hip_error(h, "hipMemcpyAsync H2D");
-            desc = s.d_desc;
-        }
-        if ((h = hipSetDevice(engine_->device())) != hipSuccess) return hip_error(h, "hipSetDevice");
-        if ((h = fk::launch_gather_desc(static_cast<const fk::GatherDesc*>(desc), (uint32_t)(B * (size_t)k_), s.d_in,
-                                        s.slot, st)) != hipSuccess)
-            return hip_error(h, "gather launch");
-        in = s.d_in;
-    } else if (!zc &&
-               (h = hipMemcpyAsync(s.d_in, s.h_in, B * (size_t)k_ * s.slot, hipMemcpyHostToDevice, st)) != hipSuccess) {
-        return hip_error(h, "hipMemcpyAsync H2D");
-    }
+    bool zc = false;
+    uint8_t* in = nullptr;
+    if (!(e = flush_input(s, B, (size_t)k_, engine_->device(), st, &zc, &in)).ok()) return e;
+    uint8_t* out = static_cast<uint8_t*>(zc ? s.out.mapped : s.out.dev);
     int rc;
     if (rs_)
         rc = fec_rs_encode_batch(ctx, k_, m_, s.maxLen, B, in, (size_t)k_ * s.slot, out, (size_t)m_ * s.slot, s.slot,
@@ -408,11 +473,10 @@ Error BatchEncoder::flushImpl(size_t* delivered) {
     else
         rc = fec_xor_encode_batch(ctx, k_, s.maxLen, B, in, (size_t)k_ * s.slot, out, s.slot, s.slot, FEC_DEVICE);
     if (rc) return codec_rc(rc);
-    if (!zc && (h = hipMemcpyAsync(s.h_out, s.d_out, B * (size_t)m_ * s.slot, hipMemcpyDeviceToHost, st)) != hipSuccess)
+    hipError_t h;
+    if (!zc && (h = hipMemcpyAsync(s.out.host, s.out.dev, B * (size_t)m_ * s.slot, hipMemcpyDeviceToHost, st)) != hipSuccess)
         return hip_error(h, "hipMemcpyAsync D2H");
-    if ((h = hipEventRecord((hipEvent_t)s.done, st)) != hipSuccess) return hip_error(h, "hipEventRecord");
-    s.inFlight = true;
-    cur_ ^= 1;
+    if (!(e = launched(s, st, &cur_)).ok()) return e;
     // the other set becomes the staging set: retire it if its batch is still out
     Set& next = sets_[cur_];
     if (next.inFlight) {
@@ -423,14 +487,12 @@ Error BatchEncoder::flushImpl(size_t* delivered) {
     return Error::nil();
 }
 
-Error BatchEncoder::waitSet(Set& s) {
-    const hipError_t h = hipEventSynchronize((hipEvent_t)s.done);
-    return h == hipSuccess ? Error::nil() : hip_error(h, "hipEventSynchronize");
+Error BatchEncoder::retire(Set& s) {
+    Error e = wait_set(s);
+    return e.ok() ? collect(s) : e;
 }
 
-Error BatchEncoder::retire(Set& s) {
-    Error e = waitSet(s);
-    if (!e.ok()) return e;
+Error BatchEncoder::collect(Set& s) {
     s.pools.clear();   // the device has read every referenced payload
     s.gather = false;
     s.inFlight = false;
@@ -440,21 +502,15 @@ Error BatchEncoder::retire(Set& s) {
     // an older holding set's blocks go out before any of this set's: raw_ only ever holds blocks
     // older than a holding set's (PeekRaw serves raw_ first)
     if (holding_ >= 0 && holding_ != idx) spill(sets_[holding_]);
-    if (raw_only) {   // hand the blocks out of h_out in place (PeekRaw)
+    if (raw_only) {   // hand the blocks out of `out` in place (PeekRaw)
         holding_ = idx;
         s.rawNext = 0;
         return Error::nil();
     }
     for (size_t i = 0; i < s.blocks.size(); ++i) {
         const Pending& p = s.blocks[i];
-        if (!p.q) {   // no queue: keep the payloads, back to back, for PopRaw
-            RawBlock rb;
-            rb.id = p.id;
-            rb.len = p.len;
-            rb.bytes.resize((size_t)m_ * p.len);
-            for (int j = 0; j < m_; ++j)
-                memcpy(rb.bytes.data() + (size_t)j * p.len, s.h_out + (i * (size_t)m_ + j) * s.slot, p.len);
-            raw_.push_back(std::move(rb));
+        if (!p.q) {   // no queue: keep the payloads for PopRaw
+            keepRaw(s, i);
             continue;
         }
         Ready r{p.q, p.tok, p.id, {}};
@@ -463,14 +519,12 @@ Error BatchEncoder::retire(Set& s) {
             // repairSymbols makes RS payloads as make([]byte, 0, MaxPacketBufferSize)[:L']
             // (reed_solomon.go:44-49) and the XOR payload as make([]byte, L) (xor.go:28-33)
             Slice pl = rs_ ? Slice::make(0, kMaxPacketBufferSize).reslice(0, p.len) : Slice::make(p.len, p.len);
-            memcpy(pl.data(), s.h_out + (i * (size_t)m_ + j) * s.slot, p.len);
+            memcpy(pl.data(), s.out.h<uint8_t>() + (i * (size_t)m_ + j) * s.slot, p.len);
             r.payloads.push_back(pl);
         }
         backlog_.push_back(std::move(r));
     }
-    s.blocks.clear();
-    s.maxLen = 0;
-    s.inFlight = false;
+    handBack(s);
     return Error::nil();
 }
 
@@ -505,16 +559,8 @@ bool BatchEncoder::pump(size_t* blocks) {
 
 Error BatchEncoder::Poll(size_t* blocks) {
     if (blocks) *blocks = 0;
-    // the older batch is the one not being staged
-    for (int i = 1; i >= 0; --i) {
-        Set& s = sets_[cur_ ^ i];
-        if (!s.inFlight) continue;
-        const hipError_t h = hipEventQuery((hipEvent_t)s.done);
-        if (h == hipErrorNotReady) break;   // later batches complete later (one stream)
-        if (h != hipSuccess) return hip_error(h, "hipEventQuery");
-        Error e = retire(s);
-        if (!e.ok()) return e;
-    }
+    Error e = visit_in_flight(sets_, cur_, true, [&](Set& s) { return collect(s); });
+    if (!e.ok()) return e;
     return pump(blocks) ? Error::nil() : Error::text("repair queue full");
 }
 
@@ -522,12 +568,8 @@ Error BatchEncoder::Drain(size_t* blocks) {
     if (blocks) *blocks = 0;
     size_t n = 0;
     Error e = flushImpl(&n);
+    if (e.ok()) e = visit_in_flight(sets_, cur_, false, [&](Set& s) { return collect(s); });
     if (!e.ok()) return e;
-    for (int i = 1; i >= 0; --i) {
-        Set& s = sets_[cur_ ^ i];
-        if (!s.inFlight) continue;
-        if (!(e = retire(s)).ok()) return e;
-    }
     const bool empty = pump(&n);
     if (blocks) *blocks = n;
     return empty ? Error::nil() : Error::text("repair queue full");
@@ -541,10 +583,6 @@ size_t BatchEncoder::InFlight() const {
 }
 
 size_t BatchEncoder::Backlog() const { return backlog_.size(); }
-
-}  // namespace fec
-
-namespace fec {
 
 // ------------------------------------------------------------------ RecoveredQueue
 
@@ -573,30 +611,16 @@ Error BatchDecoder::New(DecoderFECScheme scheme, int k, int m, size_t maxBlocks,
     out->reset();
     if (maxBlocks == 0) return Error::text("batch must hold at least one block");
     std::unique_ptr<BatchDecoder> d(new BatchDecoder(scheme, k, m, maxBlocks, std::move(engine)));
-    if (scheme == ReedSolomonFECScheme) {
-        Error err = ReedSolomonScheme::New(k, m, d->engine_, &d->rs_);
-        if (!err.ok()) return err;
-        if (k + m > FEC_MAX_DECODE_SHARDS) return codec_rc(FEC_ERR_MAX_SHARD_NUM);
-    } else if (scheme == XORFECScheme) {
-        if (m != 1) return Error::text("xor only supports 1 repair symbol");
-        if (k < 1 || k > 255) return Error::text("invalid number of source symbols");
-        d->xor_.reset(new XorScheme(d->engine_));
-    } else {
-        return Error::text("no FEC scheme");
-    }
+    Error err = make_scheme(scheme, k, m, d->engine_, &d->rs_, &d->xor_);
+    if (!err.ok()) return err;
+    if (d->rs_ && k + m > FEC_MAX_DECODE_SHARDS) return codec_rc(FEC_ERR_MAX_SHARD_NUM);
     *out = std::move(d);
     return Error::nil();
 }
 
 BatchDecoder::~BatchDecoder() {
-    for (Set& s : sets_) {
-        if (s.inFlight && s.done) (void)hipEventSynchronize((hipEvent_t)s.done);
-        if (s.done) (void)hipEventDestroy((hipEvent_t)s.done);
-        for (void* p : {(void*)s.h_in, (void*)s.h_out, (void*)s.h_masks, (void*)s.h_status, s.h_desc})
-            if (p) (void)hipHostFree(p);
-        for (void* p : {(void*)s.d_in, (void*)s.d_out, (void*)s.d_masks, (void*)s.d_status, s.d_desc})
-            if (p) (void)hipFree(p);
-    }
+    for (Set& s : sets_)   // a set still in flight completes before its buffers go
+        if (s.inFlight) (void)wait_set(s);
 }
 
 Error BatchDecoder::init() {
@@ -604,34 +628,16 @@ Error BatchDecoder::init() {
     Error e = engine_->ctx(&ctx);
     if (!e.ok()) return e;
     const size_t n = (size_t)k_ + m_;
-    const size_t in_bytes = maxBlocks_ * n * kDecSlotMax, out_bytes = maxBlocks_ * (size_t)m_ * kDecSlotMax;
+    const char* what = "staging allocation";
     for (Set& s : sets_) {
-        hipError_t h;
-        if ((h = hipHostMalloc(&s.h_in, in_bytes, hipHostMallocDefault)) != hipSuccess ||
-            (h = hipHostMalloc(&s.h_out, out_bytes, hipHostMallocDefault)) != hipSuccess ||
-            (h = hipHostMalloc(&s.h_masks, maxBlocks_ * 4, hipHostMallocDefault)) != hipSuccess ||
-            (h = hipHostMalloc(&s.h_status, maxBlocks_ * 4, hipHostMallocDefault)) != hipSuccess ||
-            (h = hipMalloc(&s.d_in, in_bytes)) != hipSuccess || (h = hipMalloc(&s.d_out, out_bytes)) != hipSuccess ||
-            (h = hipMalloc(&s.d_masks, maxBlocks_ * 4)) != hipSuccess ||
-            (h = hipMalloc(&s.d_status, maxBlocks_ * 4)) != hipSuccess ||
-            (h = hipHostMalloc(&s.h_desc, maxBlocks_ * n * sizeof(fk::GatherDesc), hipHostMallocDefault)) != hipSuccess ||
-            (h = hipMalloc(&s.d_desc, maxBlocks_ * n * sizeof(fk::GatherDesc))) != hipSuccess)
-            return hip_error(h, "staging allocation");
-        void *in_dev = nullptr, *out_dev = nullptr, *masks_dev = nullptr, *status_dev = nullptr, *desc_dev = nullptr;
-        if ((h = hipHostGetDevicePointer(&in_dev, s.h_in, 0)) != hipSuccess ||
-            (h = hipHostGetDevicePointer(&out_dev, s.h_out, 0)) != hipSuccess ||
-            (h = hipHostGetDevicePointer(&masks_dev, s.h_masks, 0)) != hipSuccess ||
-            (h = hipHostGetDevicePointer(&status_dev, s.h_status, 0)) != hipSuccess ||
-            (h = hipHostGetDevicePointer(&desc_dev, s.h_desc, 0)) != hipSuccess)
-            return hip_error(h, "hipHostGetDevicePointer");
-        s.in_dev = (uint64_t)(uintptr_t)in_dev;
-        s.out_dev = static_cast<uint8_t*>(out_dev);
-        s.masks_dev = static_cast<uint32_t*>(masks_dev);
-        s.status_dev = static_cast<int32_t*>(status_dev);
-        s.desc_dev = desc_dev;
-        hipEvent_t ev;
-        if ((h = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return hip_error(h, "hipEventCreate");
-        s.done = ev;
+        e = s.alloc(maxBlocks_ * n * kDecSlotMax, maxBlocks_ * (size_t)m_ * kDecSlotMax,
+                    maxBlocks_ * n * sizeof(fk::GatherDesc), what);
+        if (e.ok()) e = s.masks.alloc(maxBlocks_ * 4, what);
+        if (e.ok()) e = s.status.alloc(maxBlocks_ * 4, what);
+        if (!e.ok()) {
+            for (Set& t : sets_) t = Set();   // nothing is staged yet: both sets back to empty
+            return e;
+        }
     }
     ready_ = true;
     return Error::nil();
@@ -639,14 +645,8 @@ Error BatchDecoder::init() {
 
 Error BatchDecoder::stage(Block& b, uint8_t* dst, size_t slot, Pending* p, bool* nothing) {
     *nothing = false;
-    p->id = b.id;
-    p->meta = Block{};
-    p->meta.id = b.id;
-    p->meta.totNumSourceSymbols = b.totNumSourceSymbols;
-    p->meta.totNumRepairSymbols = b.totNumRepairSymbols;
-    p->meta.smallestSSID = b.smallestSSID;
-    p->meta.largestSSID = b.largestSSID;
-    p->meta.biggestSourceSymbolLenSoFar = b.biggestSourceSymbolLenSoFar;
+    p->describe(b.id, b.totNumSourceSymbols, b.totNumRepairSymbols, b.smallestSSID, b.largestSSID,
+                b.biggestSourceSymbolLenSoFar);
     if (rs_) {
         Error e = rs_->stageRecoverInput(b, dst, slot, &p->plan);
         if (!e.ok()) return e;
@@ -678,8 +678,7 @@ Error BatchDecoder::submitWith(size_t want, RecoveredQueue* q, bool* staged, Sta
     }
     Set* s = &sets_[cur_];
     if (s->inFlight) {
-        Error e = waitSet(*s);
-        if (e.ok()) e = deliver(*s, nullptr);
+        Error e = finish(*s, nullptr);
         if (!e.ok()) return e;
     }
     if (!s->blocks.empty() && (s->blocks.size() >= maxBlocks_ || want > s->slot)) {
@@ -689,18 +688,18 @@ Error BatchDecoder::submitWith(size_t want, RecoveredQueue* q, bool* staged, Sta
     }
     if (s->blocks.empty()) s->slot = want;
     const size_t idx = s->blocks.size();
-    Error e = stage_fn(s->h_in + idx * n * s->slot, s->slot, &p, &nothing);
+    Error e = stage_fn(s->in.h<uint8_t>() + idx * n * s->slot, s->slot, &p, &nothing);
     if (!e.ok() || nothing) return e;
-    s->h_masks[idx] = p.plan.mask;
+    s->masks.h<uint32_t>()[idx] = p.plan.mask;
     // every shard of the block gets a gather descriptor (its staged slot unless referenced), so a
     // set is gathered as a whole once any block of it holds a reference
-    fk::GatherDesc* desc = static_cast<fk::GatherDesc*>(s->h_desc) + idx * n;
+    fk::GatherDesc* desc = s->desc.h<fk::GatherDesc>() + idx * n;
     for (size_t i = 0; i < n; ++i) {
         if (refs && refs[i].dev) {
             desc[i] = fk::GatherDesc{refs[i].dev, refs[i].len, refs[i].frame};
             s->gather = true;
         } else {
-            desc[i] = fk::GatherDesc{s->in_dev + (uint64_t)((idx * n + i) * s->slot), (uint32_t)s->slot, fk::kNoFrame};
+            desc[i] = fk::GatherDesc{s->inDev() + (uint64_t)((idx * n + i) * s->slot), (uint32_t)s->slot, fk::kNoFrame};
         }
     }
     if (pools)
@@ -733,14 +732,7 @@ Error BatchDecoder::SubmitPayloads(BlockID id, SourceSymbolID smallest, SourceSy
         if (rep[p]) want = std::max(want, rlen[p]);
     return submitWith(want, q, staged, [&](uint8_t* dst, size_t slot, Pending* p, bool* nothing) {
         *nothing = false;
-        p->id = id;
-        p->meta = Block{};
-        p->meta.id = id;
-        p->meta.totNumSourceSymbols = k_;
-        p->meta.totNumRepairSymbols = m_;
-        p->meta.smallestSSID = smallest;
-        p->meta.largestSSID = largest;
-        p->meta.biggestSourceSymbolLenSoFar = biggest;
+        p->describe(id, k_, m_, smallest, largest, biggest);
         if (rs_) {
             Error e = rs_->stageRecoverPayloads(biggest, src, slen, rep, rlen, dst, slot, &p->plan);
             if (e.ok()) *nothing = p->plan.nothing;
@@ -772,7 +764,7 @@ Error BatchDecoder::SubmitPayloadRefs(BlockID id, SourceSymbolID smallest, Sourc
         const uint8_t* ptr = isSrc ? src[i] : rep[i - k_];
         const size_t len = isSrc ? slen[i] : rlen[i - k_];
         if (!ptr || len == 0 || (isSrc && len > (size_t)biggest)) continue;
-        uint64_t dev = 0;
+        uint64_t dev = 0;   // the block's pools so far, then the registry (as BatchEncoder::stageBlock)
         for (const auto& pl : pools)
             if ((dev = pl->DevAddr(ptr, len))) break;
         if (!dev) {
@@ -790,14 +782,7 @@ Error BatchDecoder::SubmitPayloadRefs(BlockID id, SourceSymbolID smallest, Sourc
         want, q, staged,
         [&](uint8_t* dst, size_t slot, Pending* p, bool* nothing) {
             *nothing = false;
-            p->id = id;
-            p->meta = Block{};
-            p->meta.id = id;
-            p->meta.totNumSourceSymbols = k_;
-            p->meta.totNumRepairSymbols = m_;
-            p->meta.smallestSSID = smallest;
-            p->meta.largestSSID = largest;
-            p->meta.biggestSourceSymbolLenSoFar = biggest;
+            p->describe(id, k_, m_, smallest, largest, biggest);
             Error e = rs_->stageRecoverPayloads(biggest, src, slen, rep, rlen, dst, slot, &p->plan,
                                                 reinterpret_cast<const bool*>(skip.data()));
             if (e.ok()) *nothing = p->plan.nothing;
@@ -811,8 +796,7 @@ Error BatchDecoder::Flush() { return flushImpl(nullptr); }
 Error BatchDecoder::flushImpl(size_t* delivered) {
     Set& s = sets_[cur_];
     if (s.inFlight) {
-        Error e = waitSet(s);
-        if (e.ok()) e = deliver(s, delivered);
+        Error e = finish(s, delivered);
         if (!e.ok()) return e;
     }
     if (s.blocks.empty()) return Error::nil();
@@ -821,81 +805,60 @@ Error BatchDecoder::flushImpl(size_t* delivered) {
     if (!e.ok()) return e;
     hipStream_t st = (hipStream_t)fec_ctx_stream(ctx);
     const size_t B = s.blocks.size(), n = (size_t)k_ + m_, S = s.slot;
-    const size_t nin = rs_ ? n : (size_t)k_;   // XOR stages its k inputs only
+    // XOR stages n slots a block too, and codes the first k of them
+    bool zc = false;
+    uint8_t* in = nullptr;
+    if (!(e = flush_input(s, B, n, engine_->device(), st, &zc, &in)).ok()) return e;
+    uint8_t* out = static_cast<uint8_t*>(zc ? s.out.mapped : s.out.dev);
     hipError_t h;
-    // a small set (a receive burst of a few blocks) is coded straight from and into its pinned
-    // buffers: one launch (two when gathered) and an event, where the copy form makes four copies
-    // around the kernels, each a call of its own and a copy-engine round trip (knob bat_zc: input
-    // bytes up to which; go_batch_bench burst)
-    const bool zc = B * n * S <= (size_t)std::max(0, (int)fk::g_tune.bat_zc);
-    uint8_t* in = zc ? reinterpret_cast<uint8_t*>((uintptr_t)s.in_dev) : s.d_in;
-    uint8_t* out = zc ? s.out_dev : s.d_out;
-    uint32_t* masks = zc ? s.masks_dev : s.d_masks;
-    int32_t* status = zc ? s.status_dev : s.d_status;
-    if (s.gather) {   // referenced payloads: the device pulls every shard of the set itself
-        const void* desc = s.desc_dev;
-        if (!zc) {
-            if ((h = hipMemcpyAsync(s.d_desc, s.h_desc, B * n * sizeof(fk::GatherDesc), hipMemcpyHostToDevice, st)) !=
-                hipSuccess)
-                return hip_error(h, "hipMemcpyAsync H2D");
-            desc = s.d_desc;
-        }
-        if ((h = hipSetDevice(engine_->device())) != hipSuccess) return hip_error(h, "hipSetDevice");
-        if ((h = fk::launch_gather_desc(static_cast<const fk::GatherDesc*>(desc), (uint32_t)(B * n), s.d_in, S, st)) !=
-            hipSuccess)
-            return hip_error(h, "gather launch");
-        in = s.d_in;
-    } else if (!zc && (h = hipMemcpyAsync(s.d_in, s.h_in, B * n * S, hipMemcpyHostToDevice, st)) != hipSuccess) {
-        return hip_error(h, "hipMemcpyAsync H2D");
-    }
     int rc;
     if (rs_) {
-        if (!zc && (h = hipMemcpyAsync(s.d_masks, s.h_masks, B * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+        if (!zc && (h = hipMemcpyAsync(s.masks.dev, s.masks.host, B * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
             return hip_error(h, "hipMemcpyAsync H2D");
-        rc = fec_rs_recover_batch(ctx, k_, m_, s.maxLen, B, in, n * S, in + (size_t)k_ * S, n * S, S, masks, out,
-                                  s.outSlots * S, (int)s.outSlots, status, FEC_DEVICE);
+        rc = fec_rs_recover_batch(ctx, k_, m_, s.maxLen, B, in, n * S, in + (size_t)k_ * S, n * S, S,
+                                  static_cast<uint32_t*>(zc ? s.masks.mapped : s.masks.dev), out, s.outSlots * S,
+                                  (int)s.outSlots, static_cast<int32_t*>(zc ? s.status.mapped : s.status.dev),
+                                  FEC_DEVICE);
     } else {
-        rc = fec_xor_encode_batch(ctx, (int)nin, s.maxLen, B, in, n * S, out, S, S, FEC_DEVICE);
+        rc = fec_xor_encode_batch(ctx, k_, s.maxLen, B, in, n * S, out, S, S, FEC_DEVICE);
     }
     if (rc) return codec_rc(rc);
     if (!zc) {
-        if ((h = hipMemcpyAsync(s.h_out, s.d_out, B * s.outSlots * S, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        if ((h = hipMemcpyAsync(s.out.host, s.out.dev, B * s.outSlots * S, hipMemcpyDeviceToHost, st)) != hipSuccess)
             return hip_error(h, "hipMemcpyAsync D2H");
-        if (rs_ && (h = hipMemcpyAsync(s.h_status, s.d_status, B * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        if (rs_ && (h = hipMemcpyAsync(s.status.host, s.status.dev, B * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
             return hip_error(h, "hipMemcpyAsync D2H");
     }
-    if ((h = hipEventRecord((hipEvent_t)s.done, st)) != hipSuccess) return hip_error(h, "hipEventRecord");
-    s.inFlight = true;
     s.delivered = 0;
-    cur_ ^= 1;
-    Set& next = sets_[cur_];
+    if (!(e = launched(s, st, &cur_)).ok()) return e;
+    Set& next = sets_[cur_];   // the other set becomes the staging set: deliver it if its batch is still out
     if (next.inFlight) {
-        if ((e = waitSet(next)).ok()) e = deliver(next, delivered);
-        if (!e.ok()) return e;
+        if (!(e = finish(next, delivered)).ok()) return e;
     }
     return Error::nil();
 }
 
-Error BatchDecoder::waitSet(Set& s) {
-    const hipError_t h = hipEventSynchronize((hipEvent_t)s.done);
-    return h == hipSuccess ? Error::nil() : hip_error(h, "hipEventSynchronize");
+Error BatchDecoder::finish(Set& s, size_t* blocks) {
+    Error e = wait_set(s);
+    return e.ok() ? deliver(s, blocks) : e;
 }
 
 Error BatchDecoder::deliver(Set& s, size_t* blocks) {
     const size_t B = s.blocks.size(), S = s.slot;
+    const int32_t* status = s.status.h<int32_t>();
     for (; s.delivered < B; ++s.delivered) {
         Pending& p = s.blocks[s.delivered];
         Slice out;
         Error e;
         if (rs_) {
-            if (s.h_status[s.delivered] != (int32_t)p.plan.missing.size())
-                return codec_rc(s.h_status[s.delivered] < 0 ? s.h_status[s.delivered] : FEC_ERR_HIP);
+            if (status[s.delivered] != (int32_t)p.plan.missing.size())
+                return codec_rc(status[s.delivered] < 0 ? status[s.delivered] : FEC_ERR_HIP);
             std::vector<const uint8_t*> rebuilt;
             for (size_t r = 0; r < p.plan.missing.size(); ++r)
-                rebuilt.push_back(s.h_out + (s.delivered * s.outSlots + r) * S);
+                rebuilt.push_back(s.out.h<uint8_t>() + (s.delivered * s.outSlots + r) * S);
             e = rs_->finishRecover(p.meta, p.plan, rebuilt.data(), &out);
         } else {
-            e = xor_->finishRecover(p.meta, s.h_out + s.delivered * S, S, &out);
+            e = xor_->finishRecover(p.meta, s.out.h<uint8_t>() + s.delivered * S, S, &out);
         }
         if (!e.ok()) return e;
         std::lock_guard<std::mutex> lk(p.tok->mu);
@@ -914,33 +877,16 @@ Error BatchDecoder::deliver(Set& s, size_t* blocks) {
 
 Error BatchDecoder::Poll(size_t* blocks) {
     if (blocks) *blocks = 0;
-    for (int i = 1; i >= 0; --i) {
-        Set& s = sets_[cur_ ^ i];
-        if (!s.inFlight) continue;
-        const hipError_t h = hipEventQuery((hipEvent_t)s.done);
-        if (h == hipErrorNotReady) break;
-        if (h != hipSuccess) return hip_error(h, "hipEventQuery");
-        Error e = deliver(s, blocks);
-        if (!e.ok()) return e;
-    }
-    return Error::nil();
+    return visit_in_flight(sets_, cur_, true, [&](Set& s) { return deliver(s, blocks); });
 }
 
 Error BatchDecoder::Drain(size_t* blocks) {
-    size_t before = 0;
-    Error e = flushImpl(&before);
+    size_t n = 0;
+    Error e = flushImpl(&n);
     if (blocks) *blocks = 0;
-    if (!e.ok()) return e;
-    for (int i = 1; i >= 0; --i) {
-        Set& s = sets_[cur_ ^ i];
-        if (!s.inFlight) continue;
-        if (!(e = waitSet(s)).ok()) return e;
-        size_t n = 0;
-        if (!(e = deliver(s, &n)).ok()) return e;
-        before += n;
-    }
-    if (blocks) *blocks = before;
-    return Error::nil();
+    if (e.ok()) e = visit_in_flight(sets_, cur_, false, [&](Set& s) { return deliver(s, &n); });
+    if (e.ok() && blocks) *blocks = n;
+    return e;
 }
 
 size_t BatchDecoder::Staged() const { return sets_[cur_].blocks.size(); }

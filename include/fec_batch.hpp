@@ -29,6 +29,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "fec_scheme.hpp"
@@ -115,6 +116,62 @@ private:
     size_t bytes_ = 0;
 };
 
+// One staging buffer of a batch coder: pinned host memory, the same bytes as the device sees them
+// (the allocation is mapped: small sets are coded straight from and into it, knob bat_zc), and a
+// device twin of the same size for the copy form. Move-only; frees itself. This header includes no
+// HIP: what calls it is defined in fec_batch.cpp.
+struct StageBuf {
+    void* host = nullptr;
+    void* mapped = nullptr;   // host, as the device addresses it
+    void* dev = nullptr;
+    StageBuf() = default;
+    StageBuf(StageBuf&& o) noexcept { *this = std::move(o); }
+    StageBuf& operator=(StageBuf&& o) noexcept {
+        std::swap(host, o.host);
+        std::swap(mapped, o.mapped);
+        std::swap(dev, o.dev);
+        return *this;
+    }
+    ~StageBuf();
+    // Allocates `bytes` on both sides, all or nothing: on success what it held before is freed, on
+    // failure it is unchanged. what: the label of a failed allocation (null: the failing call's name).
+    Error alloc(size_t bytes, const char* what = nullptr);
+    template <class T>
+    T* h() const {
+        return static_cast<T*>(host);
+    }
+};
+
+// A staging set's completion event (hipEvent_t), destroyed with it.
+struct StageEvent {
+    void* ev = nullptr;
+    StageEvent() = default;
+    StageEvent(StageEvent&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    StageEvent& operator=(StageEvent&& o) noexcept {
+        std::swap(ev, o.ev);
+        return *this;
+    }
+    ~StageEvent();
+};
+
+// What the staging sets of both batch coders are made of. A coder has two: one stages while the
+// other's batch is in flight.
+struct StageSet {
+    StageBuf in;     // [maxBlocks][shards per block][largest slot]
+    StageBuf out;    // [maxBlocks][m][largest slot]
+    StageBuf desc;   // [maxBlocks][shards per block] gather descriptors (fk::GatherDesc)
+    StageEvent done;
+    std::vector<std::shared_ptr<PacketPool>> pools;   // pools the batch's references point into
+    size_t slot = 0;      // S of this batch (16-byte multiple)
+    size_t maxLen = 0;    // largest shard length of this batch
+    bool gather = false;  // some shard is referenced: the device gathers the whole batch
+    bool inFlight = false;
+    // All or nothing: a failure leaves the buffers empty, everything freed. (The coders' init()
+    // empties both sets when either fails.)
+    Error alloc(size_t in_bytes, size_t out_bytes, size_t desc_bytes, const char* what = nullptr);
+    uint64_t inDev() const { return (uint64_t)(uintptr_t)in.mapped; }
+};
+
 class BatchEncoder {
 public:
     // scheme: ReedSolomonFECScheme (k, m) or XORFECScheme (k, 1). maxBlocks: blocks per batch.
@@ -178,24 +235,9 @@ private:
         BlockID id;
         size_t len;
     };
-    struct Set {
-        uint8_t* h_in = nullptr;    // pinned [maxBlocks][k][kSlotMax]
-        uint8_t* h_out = nullptr;   // pinned [maxBlocks][m][kSlotMax]
-        uint8_t* d_in = nullptr;
-        uint8_t* d_out = nullptr;
-        void* h_desc = nullptr;     // pinned [maxBlocks][k] gather descriptors (fk::GatherDesc)
-        void* d_desc = nullptr;
-        uint64_t in_dev = 0;        // device address of h_in (pinned, mapped)
-        uint8_t* out_dev = nullptr; // h_out and h_desc as the device sees them (small sets are coded
-        const void* desc_dev = nullptr;   // straight from and into pinned memory, knob bat_zc)
-        void* done = nullptr;       // hipEvent_t
+    struct Set : StageSet {     // in: [maxBlocks][k][kSlotMax]
         std::vector<Pending> blocks;
-        std::vector<std::shared_ptr<PacketPool>> pools;   // pools the batch's references point into
-        size_t slot = 0;            // S of this batch (16-byte multiple)
-        size_t maxLen = 0;          // largest L of this batch
-        bool gather = false;        // some payload is referenced: the device gathers the batch
-        bool inFlight = false;
-        size_t rawNext = 0;         // holding (completed, raw blocks kept in h_out): next to hand out
+        size_t rawNext = 0;         // holding (completed, raw blocks kept in `out`): next to hand out
     };
     struct RawBlock {               // a raw block copied out of a set that had to be reused
         BlockID id = 0;
@@ -206,7 +248,9 @@ private:
     int holding_ = -1;              // the set whose completed raw blocks are handed out in place
     // Copy a holding set's blocks not yet handed out to raw_ and free the set for staging.
     void spill(Set& s);
-    Error stageBlock(Set* s, BlockID id, const uint8_t* const* payloads, const size_t* lens, size_t biggest, bool refs,
+    void keepRaw(const Set& s, size_t i);   // block i of a completed set, copied to raw_
+    void handBack(Set& s);                  // a set all of whose blocks have gone: back to staging
+    Error stageBlock(BlockID id, const uint8_t* const* payloads, const size_t* lens, int count, bool refs,
                      RepairQueue* q);
     struct Ready {                  // an encoded block whose frames wait for queue room
         RepairQueue* q;
@@ -218,9 +262,11 @@ private:
         : scheme_(scheme), k_(k), m_(m), maxBlocks_(maxBlocks), engine_(std::move(e)) {}
     Error init();
     Error flushImpl(size_t* delivered);
-    Error waitSet(Set& s);
-    // Wait for a flushed set, move its blocks' payloads to the backlog and free the set.
+    // Wait for a flushed set and collect it.
     Error retire(Set& s);
+    // A completed set: its blocks' payloads go to the backlog and the set is free, or (raw blocks
+    // only) it becomes the holding set. Cannot fail: an Error for the walk over the sets in flight.
+    Error collect(Set& s);
     // Hand backlog frames to their queues in order; a queue that is full holds back its later
     // blocks. *blocks += blocks delivered. True when the backlog is empty afterwards.
     bool pump(size_t* blocks);
@@ -305,31 +351,21 @@ private:
         BlockID id;
         Block meta;                // id, biggest, SSID range (payload maps not kept)
         ReedSolomonScheme::RecoverPlan plan;   // RS: mask, length, missing indices
+        void describe(BlockID block, int nsrc, int nrep, SourceSymbolID smallest, SourceSymbolID largest, int biggest) {
+            id = block;
+            meta = Block{};
+            meta.id = block;
+            meta.totNumSourceSymbols = nsrc;
+            meta.totNumRepairSymbols = nrep;
+            meta.smallestSSID = smallest;
+            meta.largestSSID = largest;
+            meta.biggestSourceSymbolLenSoFar = biggest;
+        }
     };
-    struct Set {
-        uint8_t* h_in = nullptr;    // pinned [maxBlocks][n][kDecSlotMax]
-        uint8_t* h_out = nullptr;   // pinned [maxBlocks][m][kDecSlotMax]
-        uint32_t* h_masks = nullptr;
-        int32_t* h_status = nullptr;
-        uint8_t* d_in = nullptr;
-        uint8_t* d_out = nullptr;
-        uint32_t* d_masks = nullptr;
-        int32_t* d_status = nullptr;
-        void* done = nullptr;
+    struct Set : StageSet {     // in: [maxBlocks][n][kDecSlotMax]
+        StageBuf masks, status;     // [maxBlocks] present masks (uint32_t) and recover statuses (int32_t)
         std::vector<Pending> blocks;
-        size_t slot = 0, maxLen = 0, outSlots = 0, delivered = 0;
-        bool inFlight = false;
-        void* h_desc = nullptr;     // pinned [maxBlocks][n] gather descriptors (fk::GatherDesc)
-        void* d_desc = nullptr;
-        uint64_t in_dev = 0;        // h_in as the device sees it
-        // the other pinned buffers as the device sees them (small sets are coded straight from and
-        // into pinned memory: no copy engine round trips, fewer calls per flush)
-        uint8_t* out_dev = nullptr;
-        uint32_t* masks_dev = nullptr;
-        int32_t* status_dev = nullptr;
-        const void* desc_dev = nullptr;
-        bool gather = false;        // a block of the set is referenced: the device gathers the set
-        std::vector<std::shared_ptr<PacketPool>> pools;   // pools the set's references point into
+        size_t outSlots = 0, delivered = 0;
     };
     BatchDecoder(DecoderFECScheme scheme, int k, int m, size_t maxBlocks, std::shared_ptr<Engine> e)
         : scheme_(scheme), k_(k), m_(m), maxBlocks_(maxBlocks), engine_(std::move(e)) {}
@@ -345,7 +381,7 @@ private:
     Error submitWith(size_t want, RecoveredQueue* q, bool* staged, StageFn&& stage_fn,
                      const ShardRef* refs = nullptr, std::vector<std::shared_ptr<PacketPool>>* pools = nullptr);
     Error flushImpl(size_t* delivered);
-    Error waitSet(Set& s);
+    Error finish(Set& s, size_t* blocks);    // wait for a flushed set and deliver it
     Error deliver(Set& s, size_t* blocks);
 
     DecoderFECScheme scheme_;

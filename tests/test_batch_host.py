@@ -86,3 +86,28 @@ def test_batch_decoder_validates_before_device_work(B, S):
     assert not staged and err is None and len(q) == 0
     d2, err = B.BatchDecoder.new(S.XOR_FEC_SCHEME, 2, 3)
     assert d2 is None and "xor only supports 1 repair symbol" in err
+
+
+def test_batch_coders_stay_usable_after_failed_init(fec, B, S):
+    """Without a device, a valid block passes validation and the staging sets' allocation fails:
+    the coder reports the device error, holds nothing, and does the same at the next submit."""
+    if fec.device_count() > 0:
+        pytest.skip("needs a machine without a GPU: init() succeeds here")
+    no_device = fec.lib.fec_strerror(fec.FEC_ERR_NO_DEVICE).decode()
+    enc, err = B.BatchEncoder.new(S.REED_SOLOMON_FEC_SCHEME, 2, 1)
+    assert err is None
+    dec, err = B.BatchDecoder.new(S.REED_SOLOMON_FEC_SCHEME, 2, 1)
+    assert err is None
+    rq, dq = B.RepairQueue(), B.RecoveredQueue()
+    complete = S.Block.literal(tot_src=2, tot_rep=1, biggest=10, smallest=0, largest=1,
+                               sources={0: (b"\x01" * 10, 1452), 1: (b"\x02" * 7, 1452)})
+    recoverable = S.Block.literal(tot_src=2, tot_rep=1, biggest=10, smallest=0, largest=1,
+                                  sources={1: (b"\x02" * 7, 1452)}, repairs={0: b"\x03" * 12})
+    for _ in range(2):
+        assert enc.submit(complete, rq) == no_device
+        assert enc.staged == 0 and enc.in_flight == 0
+        staged, err = dec.submit(recoverable, dq)
+        assert not staged and err == no_device
+        assert dec.staged == 0 and dec.in_flight == 0
+    assert len(rq) == 0 and len(dq) == 0
+    del enc, dec
