@@ -106,6 +106,18 @@ lib.fec_probe_stream_traffic.argtypes = [_vp, _i, _sz, _sz, _vp, _sz, _vp, _sz, 
 lib.fec_probe_link.argtypes = [_vp, _sz, _i, ctypes.POINTER(ctypes.c_double)]
 
 
+lib.fec__set_tuning.argtypes = [_vp, _i, _i]
+lib.fec__tuning_name.argtypes = [_i]
+lib.fec__tuning_name.restype = ctypes.c_char_p
+
+
+def _tuning_keys():
+    keys = {}
+    while (name := lib.fec__tuning_name(len(keys))) is not None:
+        keys[name.decode()] = len(keys)
+    return keys
+
+
 class FecError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
@@ -285,22 +297,16 @@ class Codec:
         return lib.fec_sync(self._h)
 
     # Tuning knobs (tests and tools; defaults are the measured best): residency of the shipped
-    # kernels, routing among shipped kernels, host-path sizes. Keys of the library's internal,
-    # test-only fec__set_tuning() in fk::Tuning's declaration order (fec_kernels.hpp); the setting
-    # is process-wide.
-    TUNING_KEYS = {"enc_wpc": 0, "gen_wpc": 1, "dec_wpc": 2, "dir_wpc": 3, "enc_bwpc": 4, "enc_fixed": 5,
-                   "dec_wave": 6, "dec_direct": 7, "host_chunk": 8, "host_threads": 9, "bat_zc": 10,
-                   "dec_route": 11, "st_pol": 12, "dst_pol": 13,
-                   "route_wpc": 14, "route_ww": 15, "xor_wpc": 16, "enc_ww": 17, "rag_g": 18}
+    # kernels, routing among shipped kernels, host-path sizes. {name: key} of the library's internal,
+    # test-only fec__set_tuning(), read from the library's own list (fec_kernels.hpp
+    # FEC_TUNING_KNOBS, through fec__tuning_name()); the setting is process-wide.
+    TUNING_KEYS = _tuning_keys()
 
     def set_tuning(self, **knobs):
         """Set kernel-selection knobs; returns the previous values (pass them back to restore)."""
-        fn = lib.fec__set_tuning
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-        fn.restype = ctypes.c_int
         old = {}
         for name, val in knobs.items():
-            old[name] = fn(self._h, self.TUNING_KEYS[name], int(val))
+            old[name] = lib.fec__set_tuning(self._h, self.TUNING_KEYS[name], int(val))
         return old
 
     def prepare(self, k, m):

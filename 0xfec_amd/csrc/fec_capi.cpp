@@ -371,20 +371,26 @@ int fec_ctx_set_stream(fec_ctx* ctx, void* hip_stream) {
 }
 
 // Internal, test-only tuning entry point (not part of the public ABI): knob `key` of fk::Tuning
-// (fec_kernels.hpp, keys 0..kTuningKeys-1 in declaration order) set to `value`, process-wide, for
-// every ctx. Tests and tools set knobs while no other thread submits work. Returns the previous
-// value, or FEC_ERR_INVALID_ARG for an unknown key.
+// (fec_kernels.hpp FEC_TUNING_KNOBS, keys 0..kTuningKeys-1 in list order) set to `value`,
+// process-wide, for every ctx. Tests and tools set knobs while no other thread submits work.
+// Returns the previous value, or FEC_ERR_INVALID_ARG for an unknown key.
 int fec__set_tuning(fec_ctx* ctx, int key, int value) {
     if (!ctx) return FEC_ERR_INVALID_ARG;
     fk::Tuning& t = fk::g_tune;
-    std::atomic<int>* slots[fk::kTuningKeys] = {&t.enc_wpc,   &t.gen_wpc,    &t.dec_wpc,      &t.dir_wpc,
-                                                &t.enc_bwpc,  &t.enc_fixed,  &t.dec_wave,     &t.dec_direct,
-                                                &t.host_chunk, &t.host_threads, &t.bat_zc,     &t.dec_route,
-                                                &t.st_pol,     &t.dst_pol,    &t.route_wpc,
-                                                &t.route_ww,   &t.xor_wpc,
-                                                &t.enc_ww,     &t.rag_g};
+#define FEC_KNOB_SLOT(name, def) &t.name,
+    std::atomic<int>* slots[fk::kTuningKeys] = {FEC_TUNING_KNOBS(FEC_KNOB_SLOT)};
+#undef FEC_KNOB_SLOT
     if (key < 0 || key >= fk::kTuningKeys) return FEC_ERR_INVALID_ARG;
     return slots[key]->exchange(value);
+}
+
+// Internal, test-only like fec__set_tuning: the name of knob `key`, or null past the last key
+// (the Python face builds Codec.TUNING_KEYS from it).
+const char* fec__tuning_name(int key) {
+#define FEC_KNOB_NAME(name, def) #name,
+    static const char* const names[fk::kTuningKeys] = {FEC_TUNING_KNOBS(FEC_KNOB_NAME)};
+#undef FEC_KNOB_NAME
+    return key >= 0 && key < fk::kTuningKeys ? names[key] : nullptr;
 }
 
 int fec_ctx_reset_stream(fec_ctx* ctx) {
@@ -402,13 +408,7 @@ int fec_sync(fec_ctx* ctx) {
     HIP_TRY(hipMemcpy(&err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost));
     if (err) {
         HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream));
-        // 1: a block with too few shards; 2: more erasures than output slots; 4: internal (the
-        // form-3 plan kernel's LDS-alignment guard); 8: a ragged call met a block longer than its
-        // max_shard_len
-        return (err & 1)   ? FEC_ERR_TOO_FEW_SHARDS
-               : (err & 4) ? FEC_ERR_HIP
-               : (err & 2) ? FEC_ERR_INVALID_ARG
-                           : FEC_ERR_SHARD_SIZE;
+        return fk::sticky_rc(err);
     }
     return FEC_OK;
 }

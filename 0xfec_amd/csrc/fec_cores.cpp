@@ -16,10 +16,9 @@
 #include "fec_verify.hpp"
 #include "fec_wide.hpp"
 
-// Workgroups for a flat (block, chunk) item launch: one item per lane (total < 2^31).
-static int flat_grid(uint32_t total) {
-    return (int)std::max<uint64_t>(1, ((uint64_t)total + fk::kThreads - 1) / fk::kThreads);
-}
+// Workgroups for a flat (block, chunk) item launch: one item per lane (total < 2^31), never an
+// empty grid.
+static int flat_grid_nonempty(uint32_t total) { return (int)std::max<uint64_t>(1, fk::flat_grid<uint64_t>(total)); }
 
 // A batch is cut into launches of consecutive blocks: fewer than kMaxItems items (block, chunk)
 // each, and, where a launch keeps a plan record of `stride` bytes per block, at most kPlanBytes of
@@ -97,7 +96,7 @@ int rs_encode_device(fec_ctx* ctx, Code* code, const Shards& s) {
                 HIP_TRY(fk::launch_rs_encode_fixed(a, ctx->stream));
                 continue;
             }
-            HIP_TRY(fk::launch_rs_encode(a, flat_grid(a.total), ctx->stream));
+            HIP_TRY(fk::launch_rs_encode(a, flat_grid_nonempty(a.total), ctx->stream));
         }
         return FEC_OK;
     });
@@ -305,7 +304,7 @@ int rs_verify_device(fec_ctx* ctx, Code* code, const Shards& s, int32_t* status,
             fill_syndrome(a, code, r0, sl);
             a.status = status + b0;
             a.count = count;
-            HIP_TRY(fk::launch_rs_verify(a, flat_grid(a.total), ctx->stream));
+            HIP_TRY(fk::launch_rs_verify(a, flat_grid_nonempty(a.total), ctx->stream));
         }
         return FEC_OK;
     });
@@ -341,7 +340,7 @@ static int update_launches(const Code* code, const UpdateCall& u, F emit) {
 
 int rs_update_device(fec_ctx* ctx, const Code* code, const UpdateCall& u) {
     return update_launches(code, u, [&](const fk::UpdateArgs& a) -> int {
-        HIP_TRY(fk::launch_rs_update(a, flat_grid(a.total), ctx->stream));
+        HIP_TRY(fk::launch_rs_update(a, flat_grid_nonempty(a.total), ctx->stream));
         return FEC_OK;
     });
 }
@@ -390,7 +389,7 @@ int rs_locate_device(fec_ctx* ctx, const Code* code, const LocateCall& c) {
     return locate_launches(
         code, c,
         [&](const fk::LocateArgs& a) -> int {
-            HIP_TRY(fk::launch_rs_locate(a, flat_grid(a.total), ctx->stream));
+            HIP_TRY(fk::launch_rs_locate(a, flat_grid_nonempty(a.total), ctx->stream));
             return FEC_OK;
         },
         [&](const fk::LocateFinArgs& f) -> int {
@@ -515,14 +514,14 @@ static int locate_partial_launches(const Code* code, const LocatePartialCall& pc
 }
 
 static int launch_locate_slice(const LocateMultiSlice& sl, hipStream_t s) {
-    HIP_TRY(fk::launch_rs_locate_multi_scan(sl.scan, flat_grid(sl.scan.total), s));
+    HIP_TRY(fk::launch_rs_locate_multi_scan(sl.scan, flat_grid_nonempty(sl.scan.total), s));
     HIP_TRY(fk::launch_rs_locate_multi_solve(sl.solve, s));
     HIP_TRY(fk::launch_rs_locate_multi_finalize(sl.fin, s));
     return FEC_OK;
 }
 static int launch_locate_slice(const LocatePartialSlice& sl, hipStream_t s) {
     HIP_TRY(fk::launch_rs_locate_partial_plan(sl.plan, s));
-    HIP_TRY(fk::launch_rs_locate_partial_scan(sl.scan, flat_grid(sl.scan.total), s));
+    HIP_TRY(fk::launch_rs_locate_partial_scan(sl.scan, flat_grid_nonempty(sl.scan.total), s));
     HIP_TRY(fk::launch_rs_locate_partial_solve(sl.solve, s));
     HIP_TRY(fk::launch_rs_locate_partial_finalize(sl.fin, s));
     return FEC_OK;
@@ -682,7 +681,7 @@ static fk::XorArgs xor_slice(int k, const Shards& sl, bool encode) {
 int xor_encode_device(fec_ctx* ctx, int k, const Shards& s) {
     return for_flat_slices(s, [&](const Shards& sl, size_t) -> int {
         const fk::XorArgs a = xor_slice(k, sl, true);
-        HIP_TRY(fk::launch_xor_encode(a, flat_grid(a.total), ctx->stream));
+        HIP_TRY(fk::launch_xor_encode(a, flat_grid_nonempty(a.total), ctx->stream));
         return FEC_OK;
     });
 }
@@ -697,7 +696,7 @@ int xor_reconstruct_device(fec_ctx* ctx, int k, const Shards& s, const DecodeWor
         a.status = w.status;
         a.err = w.err;
         a.nblocks = (uint32_t)sl.nblocks;
-        HIP_TRY(fk::launch_xor_reconstruct(a, flat_grid(a.total), ctx->stream));
+        HIP_TRY(fk::launch_xor_reconstruct(a, flat_grid_nonempty(a.total), ctx->stream));
         return FEC_OK;
     });
 }

@@ -51,17 +51,18 @@ __global__ __launch_bounds__(kPlanThreads) void rs_plan_kernel(PlanArgs a) {
         const uint32_t mask = a.masks[b] & all;
         const uint32_t kmask = low_mask(k);   // k = 32 when m = 0
         const uint32_t e = k - __popc(mask & kmask);
+        // the rule of fec_status.hpp (classify_block), in place
         int32_t st = a.max_out ? (int32_t)e : 0;   // recover reports the rebuilt count
         if (e == 0) {
             P[lay.nout_off] = 0;
         } else if ((uint32_t)__popc(mask) < k) {
             P[lay.nout_off] = 0;
-            st = -4;  // FEC_ERR_TOO_FEW_SHARDS
-            wave_flag(a.err, 1);
+            st = kStTooFew;
+            wave_flag(a.err, kStickyTooFew);
         } else if (a.max_out && e > a.max_out) {
             P[lay.nout_off] = 0;
-            st = -1;  // FEC_ERR_INVALID_ARG: more erasures than output slots
-            wave_flag(a.err, 2);
+            st = kStSlots;
+            wave_flag(a.err, kStickySlots);
         } else if (e == 1) {
             // one erasure: x_E = inv(A[R0][E0]) * (p_R0 ^ sum_j A[R0][j] x_j)
             const uint32_t E0 = __ffs(~mask & kmask) - 1;
@@ -198,11 +199,9 @@ size_t recon_lds_bytes(uint32_t g, uint32_t k, uint32_t maxe, const PlanLayout& 
 
 hipError_t launch_rs_reconstruct(const ReconArgs& a, int grid, hipStream_t s) {
     const size_t lds = occupancy_lds(g_tune.dec_wpc, recon_lds_bytes(a.g, a.k, a.maxe, a.lay));
-    if (a.maxe <= 1) hipLaunchKernelGGL((rs_reconstruct_kernel<1>), dim3(grid), dim3(kThreads), lds, s, a);
-    else if (a.maxe <= 2) hipLaunchKernelGGL((rs_reconstruct_kernel<2>), dim3(grid), dim3(kThreads), lds, s, a);
-    else if (a.maxe <= 4) hipLaunchKernelGGL((rs_reconstruct_kernel<4>), dim3(grid), dim3(kThreads), lds, s, a);
-    else if (a.maxe <= 8) hipLaunchKernelGGL((rs_reconstruct_kernel<8>), dim3(grid), dim3(kThreads), lds, s, a);
-    else hipLaunchKernelGGL((rs_reconstruct_kernel<16>), dim3(grid), dim3(kThreads), lds, s, a);
+    with_maxe(a.maxe, [&](auto e) {
+        hipLaunchKernelGGL((rs_reconstruct_kernel<decltype(e)::value>), dim3(grid), dim3(kThreads), lds, s, a);
+    });
     return hipGetLastError();
 }
 
@@ -213,7 +212,7 @@ bool wave_recon_applies(uint32_t cps, uint32_t k, uint32_t maxe, uint32_t stride
 }
 
 hipError_t launch_rs_reconstruct_wave(const ReconArgs& a, hipStream_t s) {
-    const int grid = (int)(((uint64_t)a.nblocks * a.cps + kThreads - 1) / kThreads);
+    const int grid = (int)flat_grid((uint64_t)a.nblocks * a.cps);
     if (grid == 0) return hipSuccess;
     const size_t lds = occupancy_lds(g_tune.dec_wpc, 4 * wave_slice_bytes(a.k, a.maxe, a.lay.stride));
 #define FEC_WAVE_LAUNCH(...) hipLaunchKernelGGL((rs_reconstruct_wave_kernel<__VA_ARGS__>), dim3(grid), dim3(kThreads), lds, s, a)
@@ -222,11 +221,7 @@ hipError_t launch_rs_reconstruct_wave(const ReconArgs& a, hipStream_t s) {
     // rs_rebuild_k_kernel (fec_rebuild.hip) instead
     if (a.k == 16 && a.maxe == 8) FEC_WAVE_LAUNCH(8, 16);
     else if (a.k == 20 && a.maxe == 10) FEC_WAVE_LAUNCH(16, 20);
-    else if (a.maxe <= 1) FEC_WAVE_LAUNCH(1);
-    else if (a.maxe <= 2) FEC_WAVE_LAUNCH(2);
-    else if (a.maxe <= 4) FEC_WAVE_LAUNCH(4);
-    else if (a.maxe <= 8) FEC_WAVE_LAUNCH(8);
-    else FEC_WAVE_LAUNCH(16);
+    else with_maxe(a.maxe, [&](auto e) { FEC_WAVE_LAUNCH(decltype(e)::value); });
 #undef FEC_WAVE_LAUNCH
     return hipGetLastError();
 }

@@ -475,7 +475,7 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, const Shards& s, const uint32_
     int err = 0;
     HIP_TRY(hipMemcpyAsync(&err, ctx->d_err + 1, sizeof(int), hipMemcpyDeviceToHost, p.comp));
     HIP_TRY(hipStreamSynchronize(p.comp));
-    if (err & 4) return FEC_ERR_HIP;
+    if ((rc = fk::sticky_rc(err & fk::kStickyInternal))) return rc;
     return failed ? FEC_ERR_TOO_FEW_SHARDS : FEC_OK;
 }
 

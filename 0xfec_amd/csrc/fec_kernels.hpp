@@ -6,6 +6,9 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
+
+#include "fec_status.hpp"
 
 namespace fk {
 
@@ -68,6 +71,23 @@ inline uint32_t decode_store_policy(int dst_pol, const ShardRegion& data, const 
                    regions_apart(parity, out, len, nblocks)
                ? 3u
                : 0u;
+}
+
+// Workgroups of a flat item grid: `per` items (one per lane: a 16-byte chunk of one block) each.
+template <class T>
+__host__ __device__ constexpr T flat_grid(T items, uint32_t per = kThreads) {
+    return (items + per - 1) / per;
+}
+
+// f(std::integral_constant<int, E>) for the row count E the rebuild kernels are compiled for that
+// serves plans of up to maxe rows: 1, 2, 4, 8, else 16.
+template <class F>
+void with_maxe(uint32_t maxe, F&& f) {
+    if (maxe <= 1) f(std::integral_constant<int, 1>{});
+    else if (maxe <= 2) f(std::integral_constant<int, 2>{});
+    else if (maxe <= 4) f(std::integral_constant<int, 4>{});
+    else if (maxe <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
 }
 
 // Bits [0, n) set, for n in [0, 32] (a present mask over n shards; 1u << 32 is undefined).
@@ -162,48 +182,59 @@ struct XorArgs {
 // internal, test-only fec__set_tuning() (fec_capi.cpp): process-wide, read without locks by every
 // ctx's launches (the fields are atomic, so a concurrent write is not a data race, but the tests
 // and tools set knobs only while no other thread submits work).
+// The knobs, declared once: X(name, default), in key order (fec__set_tuning keys 0, 1, ..: the order
+// is part of what tools/go_batch_bench.c and the tests pass, so new knobs go at the end). The fields
+// of Tuning, the key count, fec__set_tuning's table and fec__tuning_name() all come from this list.
+#define FEC_TUNING_KNOBS(X)                                                                            \
+    /* resident workgroups per CU (dynamic-LDS caps, occupancy_lds; 0 = as many as fit) */             \
+    X(enc_wpc, 3)   /* RS(8,12) fixed-shape encode (2 / 4 / uncapped slower) */           \
+    X(gen_wpc, 0)   /* generic RS encode and the RS(2,3) encode */                                     \
+    X(dec_wpc, 0)   /* plan-path rebuilds */                                                           \
+    X(dir_wpc, -1)  /* direct single-erasure decode; -1: by shape (k >= 8: 3, else 0) */               \
+    X(enc_bwpc, 0)  /* bit-sliced encode (RS(16,24), RS(20,30)) */                                     \
+    /* routing among shipped kernels (tests) */                                                        \
+    X(enc_fixed, 1) /* 0: every shape by the generic encode */                                         \
+    X(dec_wave, 1)  /* 0: the workgroup-tile rebuild for long shards too */                            \
+    /* 0: no direct decode (plan path for every code); 1: direct where it applies (one output slot, */ \
+    /* or m = 1), rows from the kernel argument where the coefficient words fit it (RS(2,3): its   */ \
+    /* own kernel); 2: rows always copied from the PermTab table                                   */ \
+    X(dec_direct, 1)                                                                                   \
+    /* host paths */                                                                                   \
+    X(host_chunk, 0)   /* FEC_HOST / FEC_HOST_PINNED: blocks per staging chunk (0: 128 MiB worth) */   \
+    X(host_threads, 8) /* FEC_HOST (pageable): copy workers for the staging / scatter copies */        \
+    /* batch encoder / decoder (fec_batch.cpp): sets of at most this many input bytes are coded */     \
+    /* straight from / into their pinned buffers                                                */     \
+    X(bat_zc, 4 << 20)                                                                                 \
+    /* in-place reconstructs of RS(8,12): routed by a classify pass between the direct body and */     \
+    /* the sorted plans (fec_recover.hip); 0: the sorted-plan route for every batch             */     \
+    X(dec_route, 1)                                                                                    \
+    /* store cache policy of the fixed-shape encodes (st_pol: 1 sc1, 0 nt: RS(2,3), RS(8,12),    */    \
+    /* RS(16,24), RS(20,30)) and of the RS(8,12) direct decode (dst_pol: 3 nt sc1, 0 nt)         */    \
+    /* (fec_device.hpp st16p), and of their traffic twins                                        */    \
+    X(st_pol, 1)                                                                                       \
+    X(dst_pol, 3)                                                                                      \
+    X(route_wpc, 4) /* resident workgroups per CU of the routed in-place kernel (0: as many as fit) */ \
+    /* waves per workgroup that run the routed kernel's direct body (3: the fourth wave of each  */    \
+    /* workgroup exits at once, so the direct route runs 12 of the 16 resident waves per CU, the */    \
+    /* direct body's best residency, while the plan route keeps 16; 4: all)                      */    \
+    X(route_ww, 3)                                                                                     \
+    X(xor_wpc, 6) /* XOR encode and reconstruct (fec_xor.hip) */                                       \
+    /* waves per workgroup that take items in the RS(8,12) encode (3: the fourth stages its table */   \
+    /* words and exits, 9 working waves per CU at 3 workgroups/CU, shard loads before the barrier; */  \
+    /* 4: all)                                                                                     */  \
+    X(enc_ww, 3)                                                                                       \
+    /* ragged kernels (fec_ragged.hip), tests: blocks per tile of both, clamped to what LDS and the */ \
+    /* 32-bit item ids allow (0: a window's items / the chunks of a full-length shard)              */ \
+    X(rag_g, 0)
+
 struct Tuning {
-    // resident workgroups per CU (dynamic-LDS caps, occupancy_lds; 0 = as many as fit)
-    std::atomic<int> enc_wpc{3};    // RS(8,12) fixed-shape encode (2 / 4 / uncapped slower)
-    std::atomic<int> gen_wpc{0};    // generic RS encode and the RS(2,3) encode
-    std::atomic<int> dec_wpc{0};    // plan-path rebuilds
-    std::atomic<int> dir_wpc{-1};   // direct single-erasure decode; -1: by shape (k >= 8: 3, else 0)
-    std::atomic<int> enc_bwpc{0};   // bit-sliced encode (RS(16,24), RS(20,30))
-    // routing among shipped kernels (tests)
-    std::atomic<int> enc_fixed{1};  // 0: every shape by the generic encode
-    std::atomic<int> dec_wave{1};   // 0: the workgroup-tile rebuild for long shards too
-    std::atomic<int> dec_direct{1}; // 0: no direct decode (plan path for every code); 1: direct where it
-                                    // applies (one output slot, or m = 1), rows from the kernel
-                                    // argument where the coefficient words fit it (RS(2,3): its own
-                                    // kernel); 2: rows always copied from the PermTab table
-    // host paths
-    std::atomic<int> host_chunk{0};     // FEC_HOST / FEC_HOST_PINNED: blocks per staging chunk (0: 128 MiB worth)
-    std::atomic<int> host_threads{8};   // FEC_HOST (pageable): copy workers for the staging / scatter copies
-    std::atomic<int> bat_zc{4 << 20};   // batch encoder / decoder (fec_batch.cpp): sets of at most this many
-                                        // input bytes are coded straight from / into their pinned buffers
-    // in-place reconstructs of RS(8,12): routed by a classify pass between the direct body and the
-    // sorted plans (fec_recover.hip); 0: the sorted-plan route for every batch
-    std::atomic<int> dec_route{1};
-    // store cache policy of the fixed-shape encodes (st_pol: 1 sc1, 0 nt: RS(2,3), RS(8,12), RS(16,24),
-    // RS(20,30)) and of the RS(8,12) direct decode (dst_pol: 3 nt sc1, 0 nt) (fec_device.hpp st16p),
-    // and of their traffic twins
-    std::atomic<int> st_pol{1};
-    std::atomic<int> dst_pol{3};
-    // resident workgroups per CU of the routed in-place kernel (0: as many as fit)
-    std::atomic<int> route_wpc{4};
-    // waves per workgroup that run the routed kernel's direct body (3: the fourth wave of each
-    // workgroup exits at once, so the direct route runs 12 of the 16 resident waves per CU, the
-    // direct body's best residency, while the plan route keeps 16; 4: all)
-    std::atomic<int> route_ww{3};
-    std::atomic<int> xor_wpc{6};    // XOR encode and reconstruct (fec_xor.hip)
-    // waves per workgroup that take items in the RS(8,12) encode (3: the fourth stages its table
-    // words and exits, 9 working waves per CU at 3 workgroups/CU, shard loads before the barrier; 4: all)
-    std::atomic<int> enc_ww{3};
-    // ragged kernels (fec_ragged.hip), tests: blocks per tile of both, clamped to what LDS and the
-    // 32-bit item ids allow (0: a window's items / the chunks of a full-length shard)
-    std::atomic<int> rag_g{0};
+#define FEC_KNOB_FIELD(name, def) std::atomic<int> name{def};
+    FEC_TUNING_KNOBS(FEC_KNOB_FIELD)
+#undef FEC_KNOB_FIELD
 };
-constexpr int kTuningKeys = 19;   // fec__set_tuning keys 0..18, in the order above
+#define FEC_KNOB_COUNT(name, def) +1
+constexpr int kTuningKeys = 0 FEC_TUNING_KNOBS(FEC_KNOB_COUNT);   // fec__set_tuning keys 0..kTuningKeys-1
+#undef FEC_KNOB_COUNT
 
 // Dynamic LDS that caps residency at `wpc` workgroups per CU (160 KiB of LDS per CU on gfx950):
 // halfway between 160K/(wpc+1) and 160K/wpc, never below what the kernel itself needs.

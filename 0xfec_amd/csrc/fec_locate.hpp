@@ -18,8 +18,7 @@
 
 namespace fk {
 
-constexpr int32_t kLocateClean = -1;     // FEC_LOCATE_CLEAN
-constexpr int32_t kLocateUnknown = -2;   // FEC_LOCATE_UNKNOWN
+// (the verdicts kLocateClean and kLocateUnknown: fec_status.hpp)
 constexpr int kLocateRows = 16;          // parity rows of a pass: row 0 and up to 15 further rows
 constexpr uint32_t kLocateTabBytes = 512;
 

@@ -26,7 +26,7 @@
 
 namespace fk {
 
-constexpr int32_t kLocateTooFew = -3;   // FEC_LOCATE_TOO_FEW
+// (the verdict kLocateTooFew: fec_status.hpp)
 
 // A block's plan word: e in bits [0, 9), the radius T = min(max_bad, (m - e) / 2) in bits [16, 20), and
 // bit 31 for a block of fewer than k present shards (e > m; no radius).

@@ -117,6 +117,41 @@ __device__ __forceinline__ bool route_skips(const PlanArgs& a) {
     return a.route && *(ConstU32*)a.route == 0;
 }
 
+// ---- the parts of a segment walk that forms 2 and 3 share. Each form keeps its own index scatter,
+// sums and coefficient rows; the block head (classification by the rule of fec_status.hpp, record
+// fields, status) and the window end also stay written out in both: as helpers they changed both
+// forms' machine code.
+
+// The segment step, two parts that each form calls in its own order. The mask of block b's
+// successor in the workgroup's next segment (0: none), loaded a segment ahead of its use:
+template <uint32_t G>
+__device__ __forceinline__ uint32_t next_mask(const PlanArgs& a, uint32_t b, uint32_t sg, uint32_t segs) {
+    const uint32_t bn = b + G;
+    return (sg + 1 < segs && bn < a.nblocks) ? a.masks[bn] : 0u;
+}
+// and the barrier before segment wl of a sort window. A window's first segment waits for the
+// workgroup: tables staged (first pass), the previous window's records copied out; within a
+// window a block group's scratch is its own lanes' (wave-local).
+__device__ __forceinline__ void window_sync(uint32_t wl) {
+    if (wl == 0) __syncthreads();
+    else wave_sync();
+}
+
+// The coefficient row of a block with one erased data shard E0, inputs S:
+// x_E0 = inv(A[R0][E0]) * (p_R0 ^ sum_j A[R0][j] x_j), R0 the first present parity (e = 1 with k
+// present shards: there is one, k < 32).
+__device__ __forceinline__ void one_erasure_row(uint8_t* C, const uint8_t* S, uint32_t E0, uint32_t mask, uint32_t k,
+                                                uint32_t gl, const uint8_t* s_prows, const uint8_t* s_exp,
+                                                const uint8_t* s_log) {
+    const uint32_t R0 = __ffs(mask >> k) - 1;
+    const uint8_t* row = s_prows + R0 * k;
+    const uint32_t inv = s_exp[255 - s_log[row[E0]]];
+    if (gl < k) {
+        const uint32_t sj = S[gl];
+        C[gl] = (uint8_t)(sj < k ? (row[sj] ? s_exp[s_log[inv] + s_log[row[sj]]] : 0u) : inv);
+    }
+}
+
 template <uint32_t LPB>
 __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_sorted_kernel(PlanArgs a, uint32_t segs, uint32_t win) {
     constexpr uint32_t G = kPlanSortThreads / LPB;   // blocks per workgroup segment
@@ -156,27 +191,23 @@ __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_sorted_kernel(PlanAr
         if (base >= a.nblocks) break;   // workgroup-uniform
         const uint32_t b = base + gb;
         const bool valid = b < a.nblocks;
-        const uint32_t mask_in = mask_next;
-        // the next segment's mask loads before this segment's work
-        const uint32_t bn = b + G;
-        mask_next = (sg + 1 < segs && bn < a.nblocks) ? a.masks[bn] : 0u;
         const uint32_t wl = sg % win;   // segment within the sort window
-        // a window's first segment: tables staged (first pass), the previous window's records
-        // copied out; within a window a block group's scratch is its own lanes' (wave-local)
-        if (wl == 0) __syncthreads();
-        else wave_sync();
+        const uint32_t mask_in = mask_next;
+        mask_next = next_mask<G>(a, b, sg, segs);   // loads before this segment's work
+        window_sync(wl);
         uint8_t* P = smem + L.recs + ((size_t)wl * G + gb) * lay.stride;
         const uint32_t mask = valid ? mask_in & all : all;   // past the batch: nothing to rebuild
         const uint32_t e = k - __popc(mask & kmask);
+        // the block head: the rule of fec_status.hpp (classify_block) in place, then the record's fields
         int32_t st = a.max_out ? (int32_t)e : 0;
         uint32_t nout = 0;
         if (e != 0) {
             if ((uint32_t)__popc(mask) < k) {
-                st = -4;   // FEC_ERR_TOO_FEW_SHARDS
-                if (gl == 0) wave_flag(a.err, 1);
+                st = kStTooFew;
+                if (gl == 0) wave_flag(a.err, kStickyTooFew);
             } else if (a.max_out && e > a.max_out) {
-                st = -1;   // FEC_ERR_INVALID_ARG: more erasures than output slots
-                if (gl == 0) wave_flag(a.err, 2);
+                st = kStSlots;
+                if (gl == 0) wave_flag(a.err, kStickySlots);
             } else {
                 nout = e;
             }
@@ -203,15 +234,7 @@ __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_sorted_kernel(PlanAr
             if (gl < k) P[lay.in_off + gl] = S[gl];
             if (gl < nout) P[lay.out_off + gl] = O[gl];
             if (e == 1) {
-                // one erasure: x_E = inv(A[R0][E]) * (p_R0 ^ sum_j A[R0][j] x_j)
-                const uint32_t E0 = O[0];
-                const uint32_t R0 = __ffs(mask >> k) - 1;   // e = 1 with k present shards: a parity, k < 32
-                const uint8_t* row = s_prows + R0 * k;
-                const uint32_t inv = s_exp[255 - s_log[row[E0]]];
-                if (gl < k) {
-                    const uint32_t sj = S[gl];
-                    C[gl] = (uint8_t)(sj < k ? (row[sj] ? s_exp[s_log[inv] + s_log[row[sj]]] : 0u) : inv);
-                }
+                one_erasure_row(C, S, O[0], mask, k, gl, s_prows, s_exp, s_log);
             } else {
                 // D_p and N_r are the same sum for the shard t = s_p or i_r, over the set Y = the
                 // others X (complement form, n - k < k: sum over all n indices, dall, minus the n - k
@@ -274,10 +297,12 @@ static_assert(kV3Tables == kV2Tables, "forms 2 and 3 share sort_lds's table area
 // group scratch: S bytes [0, 32), X dwords [32, 80), O dwords [80, 128), N dwords [128, 176), 255 - D_p
 // bytes [176, 208)
 constexpr uint32_t kV3S = 0, kV3X = 32, kV3O = 80, kV3N = 128, kV3D = 176, kGroupScratch3 = 208;
+// lanes per block of form 3
+constexpr uint32_t code_lanes(uint32_t K) { return K <= 16 ? 16u : 32u; }
 
 template <uint32_t K, uint32_t M>
 __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_code_kernel(PlanArgs a, uint32_t segs, uint32_t win) {
-    constexpr uint32_t N = K + M, LPB = K <= 16 ? 16u : 32u, G = kPlanSortThreads / LPB, MAXE = M;
+    constexpr uint32_t N = K + M, LPB = code_lanes(K), G = kPlanSortThreads / LPB, MAXE = M;
     static_assert(M < K && M <= 12 && K <= LPB && N <= 32, "complement-sum codes with the scratch above");
     extern __shared__ __attribute__((aligned(128))) uint8_t smem[];
     const PlanLayout lay = a.lay;
@@ -292,7 +317,7 @@ __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_code_kernel(PlanArgs
     // the sticky error fails the call, device and host paths alike)
     const uint32_t nl_base = lds_addr(s_nl);
     if (nl_base & 127u) {
-        if (threadIdx.x == 0) atomicOr(a.err, 4);
+        if (threadIdx.x == 0) atomicOr(a.err, kStickyInternal);
         return;
     }
     uint8_t* s_prows = smem + L.prows;
@@ -324,25 +349,24 @@ __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_code_kernel(PlanArgs
         const uint32_t base = (seg0 + sg) * G;
         if (base >= a.nblocks) break;   // workgroup-uniform
         const uint32_t wl = sg % win;
-        if (wl == 0) __syncthreads();
-        else wave_sync();
+        window_sync(wl);
         const uint32_t b = base + gb;
         const bool valid = b < a.nblocks;
         const uint32_t mask_in = mask_next;
-        const uint32_t bn = b + G;
-        mask_next = (sg + 1 < segs && bn < a.nblocks) ? a.masks[bn] : 0u;
+        mask_next = next_mask<G>(a, b, sg, segs);
         uint8_t* P = smem + L.recs + ((size_t)wl * G + gb) * lay.stride;
         const uint32_t mask = valid ? mask_in & all : all;   // past the batch: nothing to rebuild
         const uint32_t e = K - __popc(mask & kmask);
+        // the block head: the rule of fec_status.hpp (classify_block) in place, then the record's fields
         int32_t st = a.max_out ? (int32_t)e : 0;
         uint32_t nout = 0;
         if (e != 0) {
             if ((uint32_t)__popc(mask) < K) {
-                st = -4;   // FEC_ERR_TOO_FEW_SHARDS
-                if (gl == 0) wave_flag(a.err, 1);
+                st = kStTooFew;
+                if (gl == 0) wave_flag(a.err, kStickyTooFew);
             } else if (a.max_out && e > a.max_out) {
-                st = -1;   // FEC_ERR_INVALID_ARG: more erasures than output slots
-                if (gl == 0) wave_flag(a.err, 2);
+                st = kStSlots;
+                if (gl == 0) wave_flag(a.err, kStickySlots);
             } else {
                 nout = e;
             }
@@ -373,15 +397,7 @@ __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_code_kernel(PlanArgs
             if (gl < K) P[lay.in_off + gl] = S[gl];
             if (gl < nout) P[lay.out_off + gl] = (uint8_t)Od[gl];
             if (e == 1) {
-                // one erasure: x_E = inv(A[R0][E]) * (p_R0 ^ sum_j A[R0][j] x_j)
-                const uint32_t E0 = Od[0];
-                const uint32_t R0 = __ffs(mask >> K) - 1;
-                const uint8_t* row = s_prows + R0 * K;
-                const uint32_t inv = s_exp[255 - s_log[row[E0]]];
-                if (gl < K) {
-                    const uint32_t sj = S[gl];
-                    P[lay.coef_off + gl] = (uint8_t)(sj < K ? (row[sj] ? s_exp[s_log[inv] + s_log[row[sj]]] : 0u) : inv);
-                }
+                one_erasure_row(P + lay.coef_off, S, Od[0], mask, K, gl, s_prows, s_exp, s_log);
             } else {
                 uint32_t x[M];
 #pragma unroll
@@ -438,41 +454,33 @@ inline uint32_t plan_segments(uint32_t nseg, uint32_t win) {
     return (segs + win - 1) / win * win;
 }
 
-template <uint32_t K, uint32_t M>
-hipError_t code_launch(const PlanArgs& a, hipStream_t s) {
-    constexpr uint32_t LPB = K <= 16 ? 16u : 32u, G = kPlanSortThreads / LPB;
-    const uint32_t nseg = (a.nblocks + G - 1) / G;
-    if (nseg == 0) return hipSuccess;
-    const uint32_t win = sort_window(G), segs = plan_segments(nseg, win);
-    const uint32_t grid = (nseg + segs - 1) / segs;
-    const size_t lds = sort_lds(M, K, G, a.lay.stride, win, kGroupScratch3).total;
-    hipLaunchKernelGGL((rs_plan_code_kernel<K, M>), dim3(grid), dim3(kPlanSortThreads), lds, s, a, segs, win);
-    return hipGetLastError();
-}
-
+// Either form's launch: LPB lanes per block, gscratch bytes of group scratch per block.
 template <uint32_t LPB>
-hipError_t sorted_launch(const PlanArgs& a, hipStream_t s) {
+hipError_t sorted_launch(const PlanArgs& a, hipStream_t s, uint32_t gscratch,
+                         void (*kernel)(PlanArgs, uint32_t, uint32_t)) {
     constexpr uint32_t G = kPlanSortThreads / LPB;
     const uint32_t nseg = (a.nblocks + G - 1) / G;
     if (nseg == 0) return hipSuccess;
     const uint32_t win = sort_window(G), segs = plan_segments(nseg, win);
     const uint32_t grid = (nseg + segs - 1) / segs;
-    const size_t lds = sort_lds(a.m, a.k, G, a.lay.stride, win).total;
-    hipLaunchKernelGGL((rs_plan_sorted_kernel<LPB>), dim3(grid), dim3(kPlanSortThreads), lds, s, a, segs, win);
+    const size_t lds = sort_lds(a.m, a.k, G, a.lay.stride, win, gscratch).total;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPlanSortThreads), lds, s, a, segs, win);
     return hipGetLastError();
 }
 
 }  // namespace
 
 hipError_t launch_rs_plan_sorted(const PlanArgs& a, hipStream_t s) {
-    if (a.k == 16 && a.m == 8 && a.maxe == 8) return code_launch<16, 8>(a, s);
-    if (a.k == 20 && a.m == 10 && a.maxe == 10) return code_launch<20, 10>(a, s);
+    if (a.k == 16 && a.m == 8 && a.maxe == 8)
+        return sorted_launch<code_lanes(16)>(a, s, kGroupScratch3, rs_plan_code_kernel<16, 8>);
+    if (a.k == 20 && a.m == 10 && a.maxe == 10)
+        return sorted_launch<code_lanes(20)>(a, s, kGroupScratch3, rs_plan_code_kernel<20, 10>);
     switch (plan_lanes(a.k)) {
-        case 2: return sorted_launch<2>(a, s);
-        case 4: return sorted_launch<4>(a, s);
-        case 8: return sorted_launch<8>(a, s);
-        case 16: return sorted_launch<16>(a, s);
-        default: return sorted_launch<32>(a, s);
+        case 2: return sorted_launch<2>(a, s, kGroupScratch, rs_plan_sorted_kernel<2>);
+        case 4: return sorted_launch<4>(a, s, kGroupScratch, rs_plan_sorted_kernel<4>);
+        case 8: return sorted_launch<8>(a, s, kGroupScratch, rs_plan_sorted_kernel<8>);
+        case 16: return sorted_launch<16>(a, s, kGroupScratch, rs_plan_sorted_kernel<16>);
+        default: return sorted_launch<32>(a, s, kGroupScratch, rs_plan_sorted_kernel<32>);
     }
 }
 

@@ -52,7 +52,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 // Lengths and prefix of tile T into LDS; returns the tile's item count and the largest `rows` of
 // its blocks that have chunks. Lane i owns block i of the tile; `rows` is that block's row count
 // (the rebuild: erased shards to rebuild; the encode: unused). With `report` (the tile's first
-// window) an oversize block gets status FEC_ERR_SHARD_SIZE and sets sticky bit 8, and with `zero`
+// window) an oversize block gets status kStShardSize and sets kStickyOversize, and with `zero`
 // every other block gets status 0 (encode: no plan kernel wrote one). Two barriers, reached by
 // every lane; LDS written by the caller before the call is visible after it.
 struct TileSum {
@@ -66,8 +66,8 @@ __device__ __forceinline__ TileSum tile_prefix(const uint32_t* lens, const RagTi
     const uint32_t len = mine ? lens[T.b0 + i] : 0u;
     if (report && mine) {
         if (len > max_len) {
-            if (status) status[T.b0 + i] = -5;   // FEC_ERR_SHARD_SIZE
-            wave_flag(err, 8);
+            if (status) status[T.b0 + i] = kStShardSize;
+            wave_flag(err, kStickyOversize);
         } else if (zero && status) {
             status[T.b0 + i] = 0;
         }

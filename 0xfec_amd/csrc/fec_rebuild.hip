@@ -275,8 +275,7 @@ __global__ __launch_bounds__(kThreads) void rs_rebuild_k_kernel(ReconArgs a) {
 
 template <int K, int R, int W, bool RP>
 hipError_t rebuild_launch(const ReconArgs& a, hipStream_t s) {
-    const uint64_t total = (uint64_t)a.nblocks * a.cps;
-    const int grid = (int)((total + kThreads - 1) / kThreads);
+    const int grid = (int)flat_grid((uint64_t)a.nblocks * a.cps);
     if (grid == 0) return hipSuccess;
     const size_t lds = occupancy_lds(g_tune.dec_wpc, kTabLds + 4 * Slice<K, R>::bytes(a.lay.stride));
     hipLaunchKernelGGL((rs_rebuild_k_kernel<K, R, W, RP>), dim3(grid), dim3(kThreads), lds, s, a);

@@ -58,22 +58,23 @@ __device__ __forceinline__ void direct_status_pass(const ReconArgs& a, uint32_t 
     if (w * 64u >= a.nblocks) return;   // wave-uniform
     const uint32_t all = low_mask(k + a.m), kmask = low_mask(k);
     const uint32_t b = w * 64u + lane;
-    uint32_t bad = 0;
+    int bad = 0;
     if (b < a.nblocks) {
         const uint32_t mask = a.masks[b] & all;
+        // the rule of fec_status.hpp (classify_block), in place
         const uint32_t e = k - __popc(mask & kmask);
         int32_t st = a.max_out ? (int32_t)e : 0;
         if (e != 0 && (uint32_t)__popc(mask) < k) {
-            st = -4;   // FEC_ERR_TOO_FEW_SHARDS
-            bad = 1;
+            st = kStTooFew;
+            bad = kStickyTooFew;
         } else if (a.max_out && e > a.max_out) {
-            st = -1;   // FEC_ERR_INVALID_ARG: more erasures than output slots
-            bad = 2;
+            st = kStSlots;
+            bad = kStickySlots;
         }
         if (a.status) a.status[b] = st;
     }
-    const bool f1 = __ballot(bad == 1) != 0, f2 = __ballot(bad == 2) != 0;
-    if (lane == 0 && (f1 || f2)) atomicOr(a.err, (f1 ? 1 : 0) | (f2 ? 2 : 0));
+    const bool f1 = __ballot(bad == kStickyTooFew) != 0, f2 = __ballot(bad == kStickySlots) != 0;
+    if (lane == 0 && (f1 || f2)) atomicOr(a.err, (f1 ? kStickyTooFew : 0) | (f2 ? kStickySlots : 0));
 }
 
 // K: compile-time data shard count (0: runtime a.k). TAB: how a wave gets the PermTabs of its
@@ -118,7 +119,7 @@ __device__ __forceinline__ void direct_body(const ReconArgs& a, const CoefWords&
             if (g >= nb) break;
             const uint32_t mask = mask_of(g) & all;
             const uint32_t e = k - __popc(mask & kmask);
-            if (e == 1 && (uint32_t)__popc(mask) >= k && !(a.max_out && e > a.max_out)) {
+            if (e == 1 && block_rebuilds(e, (uint32_t)__popc(mask), k, a.max_out)) {
                 row[g] = (__ffs(~mask & kmask) - 1) * m + (__ffs(mask >> k) - 1);   // m >= 1 here: k < 32
                 any = true;
             }
@@ -277,7 +278,8 @@ __global__ __launch_bounds__(256) void rs_route_classify_kernel(const uint32_t* 
     bool multi = false;
     for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < nblocks; b += gridDim.x * 256u) {
         const uint32_t mask = masks[b] & all;
-        multi |= k - __popc(mask & kmask) >= 2 && (uint32_t)__popc(mask) >= k;
+        const uint32_t e = k - __popc(mask & kmask);
+        multi |= e >= 2 && block_rebuilds(e, (uint32_t)__popc(mask), k, 0);   // in place
     }
     if (__ballot(multi) != 0 && __lane_id() == 0) found = 1;   // plain LDS store: any writer wins
     __syncthreads();
@@ -296,7 +298,7 @@ __global__ __launch_bounds__(kThreads) void rs_reconstruct_routed_kernel(ReconAr
     } else if constexpr (WW == kThreads / 64) {
         wave_body<MAXE, 0>(a, smem, xcd_order());
     } else {
-        const uint32_t g4 = (a.nblocks * a.cps + kThreads - 1) / kThreads;
+        const uint32_t g4 = flat_grid(a.nblocks * a.cps);
         if (blockIdx.x >= g4) return;
         wave_body<MAXE, 0>(a, smem, xcd_order_of(blockIdx.x, g4));
     }
@@ -384,7 +386,7 @@ hipError_t launch_rs_route_classify(const ReconArgs& a, uint32_t* route, hipStre
 hipError_t launch_rs_reconstruct_routed(const ReconArgs& a, hipStream_t s) {
     const uint64_t total = (uint64_t)a.nblocks * a.cps;
     const bool w3 = g_tune.route_ww == 3;
-    const int flat = (int)((total + (w3 ? 191 : kThreads - 1)) / (w3 ? 192 : kThreads));
+    const int flat = (int)flat_grid(total, w3 ? 192 : kThreads);
     if (flat == 0) return hipSuccess;
     CoefWords cw{};
     memcpy(cw.w, a.single_coef_host, (size_t)a.k * a.m * ((a.k + 3) / 4) * 4);
@@ -400,23 +402,19 @@ hipError_t launch_rs_reconstruct_routed(const ReconArgs& a, hipStream_t s) {
     const size_t own = std::max(4 * direct_wave_bytes(a.k), 4 * wave_slice_bytes(a.k, a.maxe, a.lay.stride));
     const size_t lds = occupancy_lds(wpc, own);
     // in place: nt stores (decode_store_policy)
-    if (w3) {
-        if (a.maxe <= 4)
-            hipLaunchKernelGGL((rs_reconstruct_routed_kernel<4, 8, 1, 0, 3>), dim3(flat), dim3(kThreads), lds, s, a, cw);
-        else
-            hipLaunchKernelGGL((rs_reconstruct_routed_kernel<8, 8, 1, 0, 3>), dim3(flat), dim3(kThreads), lds, s, a, cw);
-    } else if (a.maxe <= 4) {
-        hipLaunchKernelGGL((rs_reconstruct_routed_kernel<4, 8, 1, 0>), dim3(flat), dim3(kThreads), lds, s, a, cw);
-    } else {
-        hipLaunchKernelGGL((rs_reconstruct_routed_kernel<8, 8, 1, 0>), dim3(flat), dim3(kThreads), lds, s, a, cw);
-    }
+    with_maxe(a.maxe, [&](auto e) {
+        // compiled for 4 and 8 rows (maxe <= 8: routed_recon_applies)
+        constexpr int E = decltype(e)::value <= 4 ? 4 : 8;
+        const dim3 g(flat), t(kThreads);
+        if (w3) hipLaunchKernelGGL((rs_reconstruct_routed_kernel<E, 8, 1, 0, 3>), g, t, lds, s, a, cw);
+        else hipLaunchKernelGGL((rs_reconstruct_routed_kernel<E, 8, 1, 0>), g, t, lds, s, a, cw);
+    });
     return hipGetLastError();
 }
 
 template <int K, int TAB, int SP = 0>
 static hipError_t direct_launch(const ReconArgs& a0, const CoefWords& cw, hipStream_t s) {
-    const uint64_t total = (uint64_t)a0.nblocks * a0.cps;
-    const int flat = (int)((total + kThreads - 1) / kThreads);
+    const int flat = (int)flat_grid((uint64_t)a0.nblocks * a0.cps);
     if (flat == 0) return hipSuccess;
     // residency by shape: 3 workgroups/CU for k >= 8 (RS(8,12) with the masks by scalar loads,
     // profiles/r05/dec_twin_r05c.log: 5.88 TB/s at 3 against 5.82 at 4, 5.76 at 5, 5.37 at 2; with
@@ -452,8 +450,7 @@ hipError_t launch_rs_recover_direct(const ReconArgs& a, hipStream_t s) {
         K2Rows rows;
         for (int e0 = 0; e0 < 2; ++e0)
             for (int j = 0; j < 2; ++j) rows.t[e0][j] = gf::make_permtab((uint8_t)(cw.w[e0] >> (8 * j)));
-        const uint64_t total = (uint64_t)a.nblocks * a.cps;
-        const int flat = (int)((total + kThreads - 1) / kThreads);
+        const int flat = (int)flat_grid((uint64_t)a.nblocks * a.cps);
         if (flat == 0) return hipSuccess;
         const int wpc = g_tune.dir_wpc >= 0 ? (int)g_tune.dir_wpc : 0;
         hipLaunchKernelGGL(rs_recover_k2m1_kernel, dim3(flat), dim3(kThreads), occupancy_lds(wpc, 0), s, a, rows);

@@ -90,6 +90,14 @@ int fec__selftest_store_policy(void) {
     return 0;
 }
 
+// Whether a record's status and row count are what the rule of fec_status.hpp (classify_block) gives
+// an in-place block with e shards to rebuild (reconstruct-some: every wanted missing shard) and np
+// shards present.
+static bool some_as_rule(int32_t st, uint32_t nout, size_t e, size_t np, uint32_t k) {
+    const fk::BlockClass c = fk::classify_block((uint32_t)e, (uint32_t)np, k, 0);
+    return st == c.status && nout == c.nout;
+}
+
 // Internal self-test (not part of the public ABI, no device needed): the records some_plan_record
 // builds (fec_some.hpp, the function rs_plan_some_kernel runs) against the systematic matrix. For
 // 64 seeded recoverable masks per code, plus all parity lost and, where m >= k, exactly k present
@@ -97,8 +105,8 @@ int fec__selftest_store_policy(void) {
 // outputs every missing shard, ascending, and row r equals M[O[r]] * inverse(rows S of M), parity
 // rows included. Then the same mask with a seeded want mask: the outputs are the wanted missing
 // shards with the rows they had, a want mask naming nothing missing gives an empty record, and a
-// mask with k - 1 present gives too-few exactly when something is to rebuild. 0 on success, else
-// 1000 * (code index + 1) + mask index + 1.
+// mask with k - 1 present gives too-few exactly when something is to rebuild. Every status and row
+// count is held to classify_block. 0 on success, else 1000 * (code index + 1) + mask index + 1.
 int fec__selftest_some_plan(void) {
     static const int shapes[][2] = {{8, 4}, {2, 1}, {20, 10}, {10, 22}, {1, 31}, {31, 1}};
     uint8_t ex768[768];
@@ -145,8 +153,9 @@ int fec__selftest_some_plan(void) {
             for (uint32_t i = 0; i < n; ++i)
                 if (!((pres >> i) & 1u)) O.push_back((uint8_t)i);
             std::fill(rec.begin(), rec.end(), 0xEE);
-            if (fk::some_plan_record(rec.data(), lay, pres | stray, 0xFFFFFFFFu, k, n, ex768, lg) != 0) return fail;
-            if (rec[lay.nout_off] != O.size()) return fail;
+            const size_t np = n - O.size();
+            int32_t st = fk::some_plan_record(rec.data(), lay, pres | stray, 0xFFFFFFFFu, k, n, ex768, lg);
+            if (!some_as_rule(st, rec[lay.nout_off], O.size(), np, k) || rec[lay.nout_off] != O.size()) return fail;
             if (O.empty()) continue;
             if (memcmp(&rec[lay.in_off], S.data(), k) || memcmp(&rec[lay.out_off], O.data(), O.size())) return fail;
             std::vector<uint8_t> inv((size_t)k * k);
@@ -161,7 +170,7 @@ int fec__selftest_some_plan(void) {
             // a want mask: only the wanted missing shards, each with the row it had
             const uint32_t want = rnd() & all;
             std::fill(rec2.begin(), rec2.end(), 0xEE);
-            if (fk::some_plan_record(rec2.data(), lay, pres, want | stray, k, n, ex768, lg) != 0) return fail;
+            st = fk::some_plan_record(rec2.data(), lay, pres, want | stray, k, n, ex768, lg);
             uint32_t r2 = 0;
             for (size_t r = 0; r < O.size(); ++r) {
                 if (!((want >> O[r]) & 1u)) continue;
@@ -170,16 +179,17 @@ int fec__selftest_some_plan(void) {
                     return fail;
                 ++r2;
             }
-            if (rec2[lay.nout_off] != r2) return fail;
-            if (fk::some_plan_record(rec2.data(), lay, pres, pres | stray, k, n, ex768, lg) != 0 || rec2[lay.nout_off])
-                return fail;
+            if (!some_as_rule(st, rec2[lay.nout_off], r2, np, k)) return fail;
+            st = fk::some_plan_record(rec2.data(), lay, pres, pres | stray, k, n, ex768, lg);
+            if (!some_as_rule(st, rec2[lay.nout_off], 0, np, k)) return fail;
             // k - 1 present: too few exactly when something is to rebuild
             uint32_t few = 0;
             for (uint32_t p = 0; p + 1 < k; ++p) few |= 1u << S[p];
-            if (fk::some_plan_record(rec2.data(), lay, few, 0xFFFFFFFFu, k, n, ex768, lg) != FEC_ERR_TOO_FEW_SHARDS ||
-                rec2[lay.nout_off])
+            st = fk::some_plan_record(rec2.data(), lay, few, 0xFFFFFFFFu, k, n, ex768, lg);
+            if (st != FEC_ERR_TOO_FEW_SHARDS || !some_as_rule(st, rec2[lay.nout_off], n - (k - 1), k - 1, k))
                 return fail;
-            if (fk::some_plan_record(rec2.data(), lay, few, few, k, n, ex768, lg) != 0 || rec2[lay.nout_off]) return fail;
+            st = fk::some_plan_record(rec2.data(), lay, few, few, k, n, ex768, lg);
+            if (!some_as_rule(st, rec2[lay.nout_off], 0, k - 1, k)) return fail;
         }
     }
     return 0;
@@ -250,9 +260,9 @@ int fec__selftest_some_wide_plan(void) {
             for (uint32_t i = 0; i < n; ++i)
                 if (!get(pres, i)) O.push_back((uint8_t)i);
             std::fill(rec.begin(), rec.end(), 0xEE);
-            if (fk::some_wide_plan_record(rec.data(), lay, with_stray(pres).data(), nullptr, k, n, ex768, lg) != 0)
-                return fail;
-            if (rec[lay.nout_off] != O.size()) return fail;
+            const size_t np = n - O.size();
+            int32_t st = fk::some_wide_plan_record(rec.data(), lay, with_stray(pres).data(), nullptr, k, n, ex768, lg);
+            if (!some_as_rule(st, rec[lay.nout_off], O.size(), np, k) || rec[lay.nout_off] != O.size()) return fail;
             if (O.empty()) continue;
             if (memcmp(&rec[lay.in_off], S.data(), k) || memcmp(&rec[lay.out_off], O.data(), O.size())) return fail;
             std::vector<uint8_t> inv((size_t)k * k);
@@ -269,8 +279,7 @@ int fec__selftest_some_wide_plan(void) {
             for (uint32_t& w : want) w = rnd();
             const Mask want_s = with_stray(want);
             std::fill(rec2.begin(), rec2.end(), 0xEE);
-            if (fk::some_wide_plan_record(rec2.data(), lay, pres.data(), want_s.data(), k, n, ex768, lg) != 0)
-                return fail;
+            st = fk::some_wide_plan_record(rec2.data(), lay, pres.data(), want_s.data(), k, n, ex768, lg);
             uint32_t r2 = 0;
             for (size_t r = 0; r < O.size(); ++r) {
                 if (!get(want, O[r])) continue;
@@ -279,21 +288,17 @@ int fec__selftest_some_wide_plan(void) {
                     return fail;
                 ++r2;
             }
-            if (rec2[lay.nout_off] != r2) return fail;
-            if (fk::some_wide_plan_record(rec2.data(), lay, pres.data(), with_stray(pres).data(), k, n, ex768, lg) !=
-                    0 ||
-                rec2[lay.nout_off])
-                return fail;
+            if (!some_as_rule(st, rec2[lay.nout_off], r2, np, k)) return fail;
+            st = fk::some_wide_plan_record(rec2.data(), lay, pres.data(), with_stray(pres).data(), k, n, ex768, lg);
+            if (!some_as_rule(st, rec2[lay.nout_off], 0, np, k)) return fail;
             // k - 1 present: too few exactly when something is to rebuild
             Mask few{};
             for (uint32_t p = 0; p + 1 < k; ++p) put(few, S[p], true);
-            if (fk::some_wide_plan_record(rec2.data(), lay, few.data(), nullptr, k, n, ex768, lg) !=
-                    FEC_ERR_TOO_FEW_SHARDS ||
-                rec2[lay.nout_off])
+            st = fk::some_wide_plan_record(rec2.data(), lay, few.data(), nullptr, k, n, ex768, lg);
+            if (st != FEC_ERR_TOO_FEW_SHARDS || !some_as_rule(st, rec2[lay.nout_off], n - (k - 1), k - 1, k))
                 return fail;
-            if (fk::some_wide_plan_record(rec2.data(), lay, few.data(), few.data(), k, n, ex768, lg) != 0 ||
-                rec2[lay.nout_off])
-                return fail;
+            st = fk::some_wide_plan_record(rec2.data(), lay, few.data(), few.data(), k, n, ex768, lg);
+            if (!some_as_rule(st, rec2[lay.nout_off], 0, k - 1, k)) return fail;
         }
     }
     return 0;

@@ -28,7 +28,7 @@ GF_HD inline uint32_t mask_bit(const uint32_t* w, uint32_t i) { return (w[i >> 5
 //   coef[r][p] = prod_{q != p} (O[r] ^ S[q]) / (S[p] ^ S[q])      (every row by Lagrange: the shard
 //                of index o is the value at o of the polynomial through the k inputs)
 // Returns the block's status: 0 (nout = |O|, or 0 when nothing is to rebuild) or
-// FEC_ERR_TOO_FEW_SHARDS = -4 (something to rebuild, fewer than k present: nout = 0).
+// kStTooFew (something to rebuild, fewer than k present: nout = 0).
 // ex768: wide_exp768(0..767); lg: the field's log table. n <= 256.
 GF_HD inline int32_t some_wide_plan_record(uint8_t* P, const WideLayout& lay, const uint32_t* present,
                                            const uint32_t* want, uint32_t k, uint32_t n, const uint8_t* ex768,
@@ -50,7 +50,7 @@ GF_HD inline int32_t some_wide_plan_record(uint8_t* P, const WideLayout& lay, co
         }
     }
     if (!e) return 0;
-    if (np < k) return -4;
+    if (np < k) return kStTooFew;
     for (uint32_t p = k; p < ((k + 7) & ~7u); ++p) S[p] = 0;
     // D_p waits in row 0 of the coefficients; rows go high to low, so row 0 replaces each D_p right
     // after reading it (as rs_plan_kernel, fec_decode.hip)

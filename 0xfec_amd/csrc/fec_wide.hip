@@ -19,7 +19,7 @@ namespace fk {
 // missing data shards; recover (a.max_out set) reports their number and refuses more than its out
 // slots. SOME = true (wide reconstruct-some): the missing shards below n that the block's want mask
 // names (a.want null: every one), data and parity alike; in place, so a.max_out is not looked at.
-// Either way a block that has something to rebuild and fewer than k shards present gets -4.
+// Either way a block that has something to rebuild and fewer than k shards present gets kStTooFew.
 constexpr int kWidePlanWaves = kThreads / 64;
 
 struct WidePlanWave {
@@ -65,16 +65,16 @@ __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) 
         npres += (uint32_t)__popcll(bp);
         e += (uint32_t)__popcll(bl);
     }
-    // statuses and the sticky word as rs_plan_kernel (fec_decode.hip)
+    // statuses and the sticky word by the rule of fec_status.hpp (classify_block), as rs_plan_kernel
     int32_t st = max_out ? (int32_t)e : 0;   // recover reports the rebuilt count
     uint32_t nout = 0;
     if (e == 0) {
     } else if (npres < k) {
-        st = -4;  // FEC_ERR_TOO_FEW_SHARDS
-        if (lane == 0) wave_flag(a.err, 1);
+        st = kStTooFew;
+        if (lane == 0) wave_flag(a.err, kStickyTooFew);
     } else if (max_out && e > max_out) {
-        st = -1;  // FEC_ERR_INVALID_ARG: more erasures than output slots
-        if (lane == 0) wave_flag(a.err, 2);
+        st = kStSlots;
+        if (lane == 0) wave_flag(a.err, kStickySlots);
     } else {
         // <= rows: a recoverable block misses at most m shards, at most min(k, m) of them data, and
         // e <= max_out here

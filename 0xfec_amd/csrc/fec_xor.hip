@@ -72,9 +72,9 @@ __global__ __launch_bounds__(kThreads) void xor_reconstruct_kernel(XorArgs a) {
             if (b < a.nblocks) {
                 const uint32_t miss = ~a.masks[b] & all;
                 fail = __popc(miss) > 1 && (miss & low_mask(k));
-                if (a.status) a.status[b] = fail ? -4 : 0;
+                if (a.status) a.status[b] = fail ? kStTooFew : 0;
             }
-            if (__ballot(fail) != 0 && lane == 0) atomicOr(a.err, 1);
+            if (__ballot(fail) != 0 && lane == 0) atomicOr(a.err, kStickyTooFew);
         }
     }
     const uint32_t i0 = xcd_order() * kThreads + (wave << 6);
