@@ -75,6 +75,9 @@ lib.fec_ctx_stream.restype = _vp
 lib.fec_sync.argtypes = [_vp]
 lib.fec_rs_matrix.argtypes = [_i, _i, _vp]
 lib.fec_rs_prepare.argtypes = [_vp, _i, _i]
+lib.fec_rs_matrix_kind.argtypes = [_i, _i, _i, _vp]
+lib.fec_ctx_set_matrix.argtypes = [_vp, _i]
+lib.fec_ctx_get_matrix.argtypes = [_vp, ctypes.POINTER(_i)]
 lib.fec_rs_encode_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_rs_reconstruct_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_recover_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _i, _vp, _i]
@@ -141,11 +144,30 @@ def device_count():
     return n.value
 
 
-def rs_matrix(k, m):
-    """n x k systematic matrix of RS(k, m) (klauspost reedsolomon.New default); no device."""
+# The matrix kinds (fec_hip_matrix.h): klauspost's default, and its WithCauchyMatrix.
+FEC_MATRIX_VANDERMONDE, FEC_MATRIX_CAUCHY = 0, 1
+MATRIX_KINDS = {"vandermonde": FEC_MATRIX_VANDERMONDE, "cauchy": FEC_MATRIX_CAUCHY}
+
+
+def _matrix_kind(matrix):
+    """A kind number from a name of MATRIX_KINDS or a number (unknown numbers are the library's to refuse)."""
+    if isinstance(matrix, str):
+        if matrix not in MATRIX_KINDS:
+            raise ValueError("unknown matrix %r (one of %s)" % (matrix, ", ".join(sorted(MATRIX_KINDS))))
+        return MATRIX_KINDS[matrix]
+    return int(matrix)
+
+
+def rs_matrix(k, m, kind=0):
+    """n x k systematic matrix of RS(k, m): kind 0 / "vandermonde" klauspost reedsolomon.New's default,
+    1 / "cauchy" its WithCauchyMatrix; no device."""
     import numpy as np
     out = np.zeros((k + m, k), dtype=np.uint8)
-    _check(lib.fec_rs_matrix(k, m, out.ctypes.data), "fec_rs_matrix")
+    kind = _matrix_kind(kind)
+    if kind == FEC_MATRIX_VANDERMONDE:
+        _check(lib.fec_rs_matrix(k, m, out.ctypes.data), "fec_rs_matrix")
+    else:
+        _check(lib.fec_rs_matrix_kind(kind, k, m, out.ctypes.data), "fec_rs_matrix_kind")
     return out
 
 
@@ -244,13 +266,29 @@ class Codec:
     """One device context (one HIP stream). Batch entry points over [B, n, S] uint8 arrays:
     numpy arrays and pageable CPU tensors run the FEC_HOST path (staged through pinned memory),
     pinned CPU tensors the FEC_HOST_PINNED path (direct DMA), CUDA tensors the FEC_DEVICE path
-    (asynchronous on the ctx stream; call sync())."""
+    (asynchronous on the ctx stream; call sync()). matrix: the code matrix of the RS calls,
+    "vandermonde" (klauspost's default) or "cauchy" (its WithCauchyMatrix); see set_matrix()."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, matrix="vandermonde"):
+        kind = _matrix_kind(matrix)
         h = _vp()
         _check(lib.fec_ctx_create(device, ctypes.byref(h)), "fec_ctx_create")
         self._h = h
         self.device = device
+        if kind != FEC_MATRIX_VANDERMONDE:
+            self.set_matrix(kind)
+
+    def set_matrix(self, matrix):
+        """The matrix kind (a name of MATRIX_KINDS or its number) of every RS call made from now on
+        (fec_ctx_set_matrix); legal between calls without a sync. The XOR calls ignore it."""
+        return _check(lib.fec_ctx_set_matrix(self._h, _matrix_kind(matrix)), "fec_ctx_set_matrix")
+
+    @property
+    def matrix(self):
+        """The name of the ctx's matrix kind (fec_ctx_get_matrix)."""
+        kind = _i(-1)
+        _check(lib.fec_ctx_get_matrix(self._h, ctypes.byref(kind)), "fec_ctx_get_matrix")
+        return next(name for name, v in MATRIX_KINDS.items() if v == kind.value)
 
     def close(self):
         if self._h:

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <functional>
 
+#include "../../include/fec_hip_matrix.h"
 #include "../../include/fec_hip_some_wide.h"
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
@@ -62,7 +63,7 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; 
 int get_code(fec_ctx* ctx, int k, int m, Code** out) {
     if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
     if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
-    auto key = std::make_pair(k, m);
+    auto key = std::make_tuple(ctx->kind, k, m);
     auto it = ctx->codes.find(key);
     if (it != ctx->codes.end()) {
         *out = &it->second;
@@ -71,8 +72,11 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
     Code c;
     c.k = k;
     c.m = m;
-    c.matrix = rs::build_matrix(k, k + m);
+    c.kind = ctx->kind;
+    c.matrix = rs::build_matrix_kind(c.kind, k, k + m);
     if (c.matrix.empty()) return FEC_ERR_INV_SHARD_NUM;
+    c.logv = rs::grs_logv(c.kind, k, k + m);
+    if (c.kind != rs::kMatrixVandermonde) HIP_TRY(c.d_logv.upload(c.logv.data(), c.logv.size()));
     if (m > 0) {
         std::vector<uint32_t> tabs((size_t)m * k * 8);
         for (int r = 0; r < m; ++r)
@@ -141,7 +145,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             // the locate-multi call's coefficients as PermTabs, then the field's tables
             // (fec_locate_multi.hpp)
             uint8_t A[fk::kLocateMultiRows * fk::kLocateMultiRows];
-            fk::locate_multi_table(A, (uint32_t)k, (uint32_t)m);
+            fk::locate_multi_table(A, (uint32_t)k, (uint32_t)m, c.logv.data());
             std::vector<uint32_t> lm(fk::locate_multi_tab_words((uint32_t)m), 0);
             for (int i = 0; i < m * m; ++i) {
                 const gf::PermTab t = gf::make_permtab(A[i]);
@@ -168,7 +172,8 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             unsigned d = 0;
             for (int t = 0; t < k + m; ++t)
                 if (t != sidx) d += gf::kTables.log[sidx ^ t];
-            dall[sidx] = (uint8_t)(d % 255u);
+            // (+ log v of the shard: the complement sums D_s and N_o both start from this entry)
+            dall[sidx] = (uint8_t)((d + c.logv[(size_t)sidx]) % 255u);
         }
         HIP_TRY(c.d_dall.upload(dall, FEC_MAX_DECODE_SHARDS));
     }
@@ -420,6 +425,30 @@ int fec_rs_matrix(int k, int m, uint8_t* out) {
     std::vector<uint8_t> mat = rs::build_matrix(k, k + m);
     if (mat.empty()) return FEC_ERR_INV_SHARD_NUM;
     memcpy(out, mat.data(), mat.size());
+    return FEC_OK;
+}
+
+// The matrix kinds (fec_hip_matrix.h). Neither ctx call touches the device: the kind only chooses
+// which cached Code the next RS call looks up (get_code); queued launches hold their own Code's tables.
+int fec_rs_matrix_kind(int kind, int k, int m, uint8_t* out) {
+    if (!out || kind < 0 || kind >= rs::kMatrixKinds) return FEC_ERR_INVALID_ARG;
+    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
+    const std::vector<uint8_t> mat = rs::build_matrix_kind(kind, k, k + m);
+    if (mat.empty()) return FEC_ERR_INV_SHARD_NUM;
+    memcpy(out, mat.data(), mat.size());
+    return FEC_OK;
+}
+
+int fec_ctx_set_matrix(fec_ctx* ctx, int kind) {
+    if (!ctx || kind < 0 || kind >= rs::kMatrixKinds) return FEC_ERR_INVALID_ARG;
+    ctx->kind = kind;
+    return FEC_OK;
+}
+
+int fec_ctx_get_matrix(fec_ctx* ctx, int* kind) {
+    if (!ctx || !kind) return FEC_ERR_INVALID_ARG;
+    *kind = ctx->kind;
     return FEC_OK;
 }
 

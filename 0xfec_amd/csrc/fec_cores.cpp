@@ -92,8 +92,11 @@ int rs_encode_device(fec_ctx* ctx, Code* code, const Shards& s) {
             a.dytabs = (r0 == 0 && (int)a.m == code->m) ? code->d_dytabs.p : nullptr;
             a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {s.data, s.dbs, s.ss, (uint64_t)k},
                                            {s.parity, s.pbs, s.pss, (uint64_t)code->m}, s.len, s.nblocks);
-            if (fk::fixed_encode_applies((uint32_t)k, a.m, a.dytabs != nullptr)) {
-                HIP_TRY(fk::launch_rs_encode_fixed(a, ctx->stream));
+            // (the fixed shapes are chosen by this code's own matrix: its kind, and for RS(2,3) its row)
+            const fk::FixedEncode fx = fk::fixed_encode((uint32_t)k, a.m, a.dytabs != nullptr, code->kind,
+                                                        code->matrix.data() + (size_t)k * k);
+            if (fx != fk::FixedEncode::none) {
+                HIP_TRY(fk::launch_rs_encode_fixed(a, fx, code->kind, ctx->stream));
                 continue;
             }
             HIP_TRY(fk::launch_rs_encode(a, flat_grid_nonempty(a.total), ctx->stream));
@@ -118,6 +121,7 @@ static void fill_recon_slice(fk::PlanArgs& p, fk::ReconArgs& a, fec_ctx* ctx, co
     p.lay = lay;
     p.max_out = c.out.base ? c.out.slots : 0;
     p.dall = code->d_dall;   // (read by the sorted plans only)
+    p.logv = code->d_logv;   // (null for the default matrix)
     a.data = c.s.data;
     a.parity = c.s.parity;
     a.dbs = c.s.dbs;
@@ -260,7 +264,7 @@ static int rs_rebuild_tiles(fec_ctx* ctx, uint32_t k, uint32_t rows, const Shard
 // form with max_out output slots (0: in place).
 static hipError_t plan_wide_slice(fec_ctx* ctx, uint32_t k, uint32_t m, uint32_t rows, const DecodeWords& words,
                                   const uint32_t* want, uint32_t max_out, bool some, size_t b0, size_t nb,
-                                  const fk::WideLayout& lay) {
+                                  const fk::WideLayout& lay, const uint8_t* logv) {
     const DecodeWords w = words.blocks(b0);
     fk::WidePlanArgs p{};
     p.masks = w.masks;
@@ -276,19 +280,34 @@ static hipError_t plan_wide_slice(fec_ctx* ctx, uint32_t k, uint32_t m, uint32_t
     p.max_out = max_out;
     p.lay = lay;
     p.div_k = fk::make_fastdiv(k);
+    p.logv = logv;
     return fk::launch_rs_plan_wide(p, some, ctx->stream);
+}
+
+// The log v table of the ctx's code for (k, m), for the plan kernels that take no Code (null for the
+// default matrix). The entry points have looked the code up already, so this finds it cached.
+static int code_logv(fec_ctx* ctx, int k, int m, const uint8_t** logv) {
+    Code* code = nullptr;
+    const int rc = get_code(ctx, k, m, &code);
+    if (rc) return rc;
+    *logv = code->d_logv;
+    return FEC_OK;
 }
 
 // Wide reconstruct / recover (fec_wide.hip): present masks of mask_words words per block, codes of
 // up to 256 shards.
 int rs_reconstruct_wide_device(fec_ctx* ctx, int ki, int mi, const ReconCall& c) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    const uint8_t* logv = nullptr;
+    const int rc = code_logv(ctx, ki, mi, &logv);
+    if (rc) return rc;
     uint32_t rows = std::max<uint32_t>(1, std::min(k, m));
     if (c.out.base) rows = std::min(rows, c.out.slots);
     const uint32_t max_out = c.out.base ? c.out.slots : 0;
     return rs_rebuild_tiles(ctx, k, rows, c.s, c.out, false,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
-                                return plan_wide_slice(ctx, k, m, rows, c.w, nullptr, max_out, false, b0, nb, lay);
+                                return plan_wide_slice(ctx, k, m, rows, c.w, nullptr, max_out, false, b0, nb, lay,
+                                                       logv);
                             });
 }
 
@@ -563,6 +582,9 @@ int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartial
 int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
                                const uint32_t* want) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
+    const uint8_t* logv = nullptr;
+    const int rc = code_logv(ctx, ki, mi, &logv);
+    if (rc) return rc;
     return rs_rebuild_tiles(ctx, k, fk::some_rows(m), s, {}, true,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
                                 const DecodeWords w = words.blocks(b0);
@@ -576,6 +598,7 @@ int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, co
                                 p.n = k + m;
                                 p.nblocks = (uint32_t)nb;
                                 p.lay = lay;
+                                p.logv = logv;
                                 return fk::launch_rs_plan_some(p, ctx->stream);
                             });
 }
@@ -586,9 +609,12 @@ int rs_reconstruct_some_wide_device(fec_ctx* ctx, int ki, int mi, const Shards& 
                                     const uint32_t* want) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
     const uint32_t rows = fk::some_rows(m);
+    const uint8_t* logv = nullptr;
+    const int rc = code_logv(ctx, ki, mi, &logv);
+    if (rc) return rc;
     return rs_rebuild_tiles(ctx, k, rows, s, {}, true,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
-                                return plan_wide_slice(ctx, k, m, rows, words, want, 0, true, b0, nb, lay);
+                                return plan_wide_slice(ctx, k, m, rows, words, want, 0, true, b0, nb, lay, logv);
                             });
 }
 

@@ -7,6 +7,7 @@
 
 #include <initializer_list>
 #include <map>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -37,14 +38,17 @@ struct DevBuf {
 
 struct Code {
     int k = 0, m = 0;
+    int kind = 0;                  // FEC_MATRIX_* (fec_hip_matrix.h)
     std::vector<uint8_t> matrix;   // n x k
+    std::vector<uint8_t> logv;     // n bytes: log of shard r's multiplier v_r (rs_matrix.hpp grs_logv; zeros for kind 0)
+    DevBuf<uint8_t> d_logv;        // the same on the device; null for kind 0 (the plan kernels test it)
     DevBuf<uint8_t> d_prows;       // m x k
     DevBuf<uint32_t> d_tabs;       // m x k PermTabs
     DevBuf<uint32_t> d_dytabs;     // dyadic codes: leaf PermTabs of the split-recursive encode
     DevBuf<uint32_t> d_single;     // single-erasure decode tables (fk::direct_table_words), when small
     DevBuf<uint32_t> d_single_coef;      // their coefficient bytes, (k*m) rows of ceil(k/4) dwords
     std::vector<uint32_t> single_coef;   // host copy
-    DevBuf<uint8_t> d_dall;        // n bytes: sum_{t != s} log(s ^ t) mod 255 (sorted plans)
+    DevBuf<uint8_t> d_dall;        // n bytes: log v_s + sum_{t != s} log(s ^ t) mod 255 (sorted plans)
     DevBuf<uint8_t> d_loctab;      // m > 0: the locate call's table (fec_locate.hpp locate_table)
     DevBuf<uint32_t> d_loc_carry;  // k > 128, m > 16: PermTabs of locate's later passes, a slab per pass
     DevBuf<uint32_t> d_lmtab;      // 1 <= m <= 16: the locate-multi call's table (fec_locate_multi.hpp)
@@ -152,7 +156,8 @@ struct fec_ctx {
     int device = 0;
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
-    std::map<std::pair<int, int>, Code> codes;
+    int kind = 0;            // the matrix kind of the RS calls made from now on (fec_hip_matrix.h)
+    std::map<std::tuple<int, int, int>, Code> codes;   // by (kind, k, m); entries stay until the ctx goes
     Work main;               // scratch of the kernels on `own` / the caller's stream
     Work* work = &main;      // scratch of the kernels on `stream` (on_stream switches both)
     int* d_err = nullptr;    // [0] sticky device-path error, [1] host-path error
@@ -178,6 +183,7 @@ inline size_t round16(size_t x) { return (x + 15) & ~size_t(15); }
 
 // ---------------------------------------------------------------- fec_capi.cpp
 int select_device(fec_ctx* ctx);
+// The ctx's code for (ctx->kind, k, m), built and cached on first use.
 int get_code(fec_ctx* ctx, int k, int m, Code** out);
 // Grow the buffers that share capacity *cap (counted in units of `unit` bytes) to hold n units:
 // pinned host memory where `pinned`, else device memory. No stream may still use the old ones.
@@ -203,6 +209,7 @@ struct ReconCall {
     ReconCall blocks(size_t b0, size_t nb) const { return {s.blocks(b0, nb), w.blocks(b0), out.blocks(b0)}; }
 };
 int rs_reconstruct_device(fec_ctx* ctx, Code* code, const ReconCall& c);
+// (the wide and the reconstruct-some cores look their code up themselves, for its d_logv)
 int rs_reconstruct_wide_device(fec_ctx* ctx, int k, int m, const ReconCall& c);
 int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, const ReconCall& c, const uint32_t* lens);
 int rs_verify_device(fec_ctx* ctx, Code* code, const Shards& s, int32_t* status, uint32_t* count);

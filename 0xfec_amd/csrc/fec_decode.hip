@@ -101,12 +101,13 @@ __global__ __launch_bounds__(kPlanThreads) void rs_plan_kernel(PlanArgs a) {
                 uint32_t d = 0;
                 for (uint32_t q = 0; q < k; ++q)
                     if (q != p) d += s_log[sp ^ S[q]];
+                if (a.logv) d += a.logv[sp];   // (PlanArgs::logv: shard s is v_s p(s))
                 C[p] = (uint8_t)(d % 255u);
             }
             // rows high to low: row 0 overwrites each D_p right after reading it
             for (uint32_t r = e; r-- > 0;) {
                 const uint32_t i = P[lay.out_off + r];
-                uint32_t nsum = 0;
+                uint32_t nsum = a.logv ? a.logv[i] : 0u;
                 for (uint32_t q = 0; q < k; ++q) nsum += s_log[i ^ S[q]];
                 for (uint32_t p = 0; p < k; ++p) {
                     const uint32_t v = nsum + 2u * 255u - s_log[i ^ S[p]] - C[p];

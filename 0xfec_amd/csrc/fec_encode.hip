@@ -210,10 +210,12 @@ __global__ __launch_bounds__(kThreads) void rs_encode_fixed_kernel(EncodeArgs a)
 // (shared sub-sums, three-input XORs, no tables), and turns the parity planes back into bytes.
 // RS(16,24): 2 x 48 ops of transposes per shard plus 1202 network ops per 32 bytes, against 54
 // v_perm products of the dyadic body per 16 bytes.
-template <int K, int M>
+// KIND: the matrix the network was generated from (FEC_MATRIX_*; 0, the default matrix, is the
+// templates' default, so its instantiations are named and compiled as before the kinds existed).
+template <int K, int M, int KIND = 0>
 struct BsShape;   // G: shards per network group
-template <int K, int M, int GI>
-__device__ __forceinline__ void bs_grp(const uint32_t (&x)[BsShape<K, M>::G][8], uint32_t (&y)[M][8]);
+template <int K, int M, int GI, int KIND = 0>
+__device__ __forceinline__ void bs_grp(const uint32_t (&x)[BsShape<K, M, KIND>::G][8], uint32_t (&y)[M][8]);
 #include "fec_bitslice.inc"
 
 // In every byte column q of the 8 dwords, transpose the 8x8 bit block (row = dword i, column =
@@ -246,10 +248,10 @@ __device__ __forceinline__ void bit_transpose8(uint32_t (&w)[8]) {
 // Group GI of the network: transpose the group's raw chunks into planes, fold them into y, then
 // load the next group (streaming the next group's loads ahead of this one's network measured -0.2 %,
 // r02).
-template <int K, int M, int GI>
+template <int K, int M, int GI, int KIND = 0>
 __device__ __forceinline__ void bs_stream(const uint8_t* s0, const uint8_t* s1, uint64_t ss,
-                                          uint4 (&cur)[BsShape<K, M>::G][2], uint32_t (&y)[M][8]) {
-    constexpr int G = BsShape<K, M>::G, NG = K / G;
+                                          uint4 (&cur)[BsShape<K, M, KIND>::G][2], uint32_t (&y)[M][8]) {
+    constexpr int G = BsShape<K, M, KIND>::G, NG = K / G;
     uint4 nxt[G][2];
     uint32_t x[G][8];
 #pragma unroll
@@ -258,19 +260,19 @@ __device__ __forceinline__ void bs_stream(const uint8_t* s0, const uint8_t* s1, 
         x[j][4] = cur[j][1].x, x[j][5] = cur[j][1].y, x[j][6] = cur[j][1].z, x[j][7] = cur[j][1].w;
         bit_transpose8(x[j]);
     }
-    bs_grp<K, M, GI>(x, y);
+    bs_grp<K, M, GI, KIND>(x, y);
     if constexpr (GI + 1 < NG) {
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             nxt[j][0] = ld16<true>(s0 + (uint64_t)((GI + 1) * G + j) * ss);
             nxt[j][1] = ld16<true>(s1 + (uint64_t)((GI + 1) * G + j) * ss);
         }
-        bs_stream<K, M, GI + 1>(s0, s1, ss, nxt, y);
+        bs_stream<K, M, GI + 1, KIND>(s0, s1, ss, nxt, y);
     }
 }
 
-template <int K, int M, int SP>
-__global__ __launch_bounds__(kThreads) void rs_encode_bits_kernel(EncodeArgs a) {
+template <int K, int M, int SP, int KIND>
+__device__ __forceinline__ void encode_bits_body(const EncodeArgs& a) {
     constexpr bool NTL = true;
     // A wave takes 128 consecutive (block, chunk) items: lane l items w*128 + l and w*128 + 64 + l,
     // so each load and store instruction covers 64 consecutive chunks, as in the one-chunk
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(kThreads) void rs_encode_bits_kernel(EncodeArgs a) 
     const uint32_t b1 = fdiv(fb, a.div_cps), c1 = fb - b1 * a.cps;   // branch); its outputs are not stored
     const uint8_t* s0 = a.in + (uint64_t)b0 * a.in_bs + (uint64_t)c0 * kChunk;
     const uint8_t* s1 = a.in + (uint64_t)b1 * a.in_bs + (uint64_t)c1 * kChunk;
-    constexpr int G = BsShape<K, M>::G;
+    constexpr int G = BsShape<K, M, KIND>::G;
     uint4 g0[G][2];
 #pragma unroll
     for (int j = 0; j < G; ++j) {
@@ -294,7 +296,7 @@ __global__ __launch_bounds__(kThreads) void rs_encode_bits_kernel(EncodeArgs a) 
         g0[j][1] = ld16<NTL>(s1 + (uint64_t)j * a.ss);
     }
     uint32_t y[M][8];
-    bs_stream<K, M, 0>(s0, s1, a.ss, g0, y);
+    bs_stream<K, M, 0, KIND>(s0, s1, a.ss, g0, y);
     uint8_t* d0 = a.out + (uint64_t)b0 * a.out_bs + (uint64_t)c0 * kChunk;
     uint8_t* d1 = a.out + (uint64_t)b1 * a.out_bs + (uint64_t)c1 * kChunk;
     const uint32_t nb0 = min(a.len - c0 * kChunk, (uint32_t)kChunk);
@@ -307,11 +309,27 @@ __global__ __launch_bounds__(kThreads) void rs_encode_bits_kernel(EncodeArgs a) 
     }
 }
 
-template <int K, int M>
+// The default matrix's networks, and the Cauchy matrix's (FEC_MATRIX_CAUCHY): one body, a kernel
+// per kind, so the default kernels keep their names and their code.
+template <int K, int M, int SP>
+__global__ __launch_bounds__(kThreads) void rs_encode_bits_kernel(EncodeArgs a) {
+    encode_bits_body<K, M, SP, 0>(a);
+}
+template <int K, int M, int SP>
+__global__ __launch_bounds__(kThreads) void rs_encode_bits_cauchy_kernel(EncodeArgs a) {
+    encode_bits_body<K, M, SP, 1>(a);
+}
+
+template <int K, int M, int KIND = 0>
 static hipError_t enc_bits_dispatch(const EncodeArgs& a, hipStream_t s) {
     const int grid = (int)((a.total + 2 * kThreads - 1) / (2 * kThreads));
     if (grid == 0) return hipSuccess;
     const size_t lds = occupancy_lds(g_tune.enc_bwpc, 0);
+    if constexpr (KIND == 1) {
+        if (a.sp == 1) hipLaunchKernelGGL((rs_encode_bits_cauchy_kernel<K, M, 1>), dim3(grid), dim3(kThreads), lds, s, a);
+        else hipLaunchKernelGGL((rs_encode_bits_cauchy_kernel<K, M, 0>), dim3(grid), dim3(kThreads), lds, s, a);
+        return hipGetLastError();
+    }
     if (a.sp == 1) hipLaunchKernelGGL((rs_encode_bits_kernel<K, M, 1>), dim3(grid), dim3(kThreads), lds, s, a);
     else hipLaunchKernelGGL((rs_encode_bits_kernel<K, M, 0>), dim3(grid), dim3(kThreads), lds, s, a);
     return hipGetLastError();
@@ -341,18 +359,26 @@ hipError_t launch_rs_encode(const EncodeArgs& a, int grid, hipStream_t s) {
 
 // (k, m) shapes with an encode of their own: the reference's benchmark codes RS(2,3) (its parity
 // row, fec_encode23.hip), RS(8,12) (dyadic), RS(16,24) and its sender's RS(20,30) (bit-sliced).
-// Any other shape runs the generic kernel.
-bool fixed_encode_applies(uint32_t k, uint32_t m, bool dyadic) {
-    if (!g_tune.enc_fixed) return false;
-    return rs_encode23_applies(k, m) || (k == 8 && m == 4 && dyadic) || (k == 16 && m == 8) || (k == 20 && m == 10);
+// Any other shape runs the generic kernel. Each is tied to a matrix, so the choice looks at the code's
+// own: RS(2,3) at its parity row, the dyadic kernel at its leaf tables (present only for a dyadic
+// matrix: the default and the Cauchy RS(8,12) both are, each with its own leaves), the bit-sliced
+// networks at the kind they were generated for.
+FixedEncode fixed_encode(uint32_t k, uint32_t m, bool dyadic, int kind, const uint8_t* prows) {
+    if (!g_tune.enc_fixed) return FixedEncode::none;
+    if (rs_encode23_applies(k, m, prows)) return FixedEncode::rs23;
+    if (k == 8 && m == 4 && dyadic) return FixedEncode::dyadic84;
+    if (((k == 16 && m == 8) || (k == 20 && m == 10)) && (kind == 0 || kind == 1)) return FixedEncode::bits;
+    return FixedEncode::none;
 }
 
-hipError_t launch_rs_encode_fixed(const EncodeArgs& a, hipStream_t s) {
+hipError_t launch_rs_encode_fixed(const EncodeArgs& a, FixedEncode which, int kind, hipStream_t s) {
     if (a.total == 0) return hipSuccess;
-    if (rs_encode23_applies(a.k, a.m)) return launch_rs_encode23(a, s);
-    if (a.k == 16 && a.m == 8) return enc_bits_dispatch<16, 8>(a, s);
-    if (a.k == 20 && a.m == 10) return enc_bits_dispatch<20, 10>(a, s);
-    if (a.k == 8 && a.m == 4 && a.dytabs) {
+    if (which == FixedEncode::rs23) return launch_rs_encode23(a, s);
+    if (which == FixedEncode::bits && a.k == 16 && a.m == 8)
+        return kind == 1 ? enc_bits_dispatch<16, 8, 1>(a, s) : enc_bits_dispatch<16, 8>(a, s);
+    if (which == FixedEncode::bits && a.k == 20 && a.m == 10)
+        return kind == 1 ? enc_bits_dispatch<20, 10, 1>(a, s) : enc_bits_dispatch<20, 10>(a, s);
+    if (which == FixedEncode::dyadic84 && a.k == 8 && a.m == 4 && a.dytabs) {
         // 3 workgroups per CU (knob enc_wpc; DESIGN.md 3: the flat grid at 3 beats 2, 4 and uncapped),
         // three of each workgroup's waves taking items (knob enc_ww): 9 working waves per CU with
         // the shard loads issued before the table staging and barrier, -1.1 / -1.3 / -1.1 % time

@@ -6,14 +6,13 @@
 // in GF(2^8) (polynomial 0x11d) per byte, four bytes of a dword at once,
 //   2*v = ((v << 1) & 0xFEFEFEFE) ^ (((v >> 7) & 0x01010101) * 0x1D),
 // and no product tables: no LDS staging and no barrier, which are most of the table-driven
-// kernel's prologue in a 40-us launch of ~20 000 one-item-per-lane workgroups. The launcher
-// checks the row on the host, so any other matrix falls back to the generic kernel. Layout, tail
+// kernel's prologue in a 40-us launch of ~20 000 one-item-per-lane workgroups. The caller
+// checks the code's row on the host, so any other matrix runs the generic kernel. Layout, tail
 // handling and workgroup order are rs_encode_fixed_kernel's (fec_encode.hip).
 #include <hip/hip_runtime.h>
 
 #include "fec_device.hpp"
 #include "fec_kernels.hpp"
-#include "rs_matrix.hpp"
 
 namespace fk {
 namespace {
@@ -42,18 +41,13 @@ __global__ __launch_bounds__(kThreads) void rs_encode23_kernel(EncodeArgs a) {
     st16p<SP>(a.out + (uint64_t)b * a.out_bs + (uint64_t)c * kChunk, keep_bytes(p, nb));
 }
 
-bool row_is_3_2() {
-    static const bool yes = [] {
-        const std::vector<uint8_t> mx = rs::build_matrix(2, 3);
-        return mx.size() == 6 && mx[4] == 3 && mx[5] == 2;
-    }();
-    return yes;
-}
-
 }  // namespace
 
-// The code is RS(2,3) with klauspost's [3 2] parity row.
-bool rs_encode23_applies(uint32_t k, uint32_t m) { return k == 2 && m == 1 && row_is_3_2(); }
+// The code is RS(2,3) and its parity row (prows, the code's own matrix) is klauspost's default [3 2];
+// the Cauchy row 8e f4 is not.
+bool rs_encode23_applies(uint32_t k, uint32_t m, const uint8_t* prows) {
+    return k == 2 && m == 1 && prows && prows[0] == 3 && prows[1] == 2;
+}
 
 // RS(2,3) encode with the fixed kernels' argument block (16-byte aligned layout, pad-zero tail);
 // the caller has checked rs_encode23_applies.

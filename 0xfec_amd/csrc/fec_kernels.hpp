@@ -115,6 +115,11 @@ struct PlanArgs {
     PlanLayout lay;
     uint32_t max_out;          // recover: output slots per block (0: in place, unlimited)
     const uint8_t* dall;       // sorted plans: per shard index s < n, sum_{t < n, t != s} log(s ^ t) mod 255
+                               // (+ logv[s]: the complement sums need nothing else of logv)
+    // Codes whose shard r is v_r p(r) (the Cauchy matrix; rs_matrix.hpp grs_logv): log v_r per shard
+    // index, added to D_s and N_o of the Lagrange plans, each for its own shard. Null for the default
+    // matrix (v = 1): a uniform test, and the sums are then formed as they were.
+    const uint8_t* logv;
     // routed in-place form (fec_recover.hip): the classify pass's word; zero (no block needs more than
     // the direct body) makes the plan kernel exit at once (null: always plan)
     const uint32_t* route;
@@ -253,9 +258,13 @@ extern size_t g_max_lds;   // LDS per workgroup the device allows (set at ctx cr
 hipError_t launch_rs_encode(const EncodeArgs& a, int grid, hipStream_t s);
 // Encodes compiled for one code (flat grid): RS(2,3), RS(8,12) (dyadic: leaf tables given),
 // RS(16,24), RS(20,30).
-bool fixed_encode_applies(uint32_t k, uint32_t m, bool dyadic);
-hipError_t launch_rs_encode_fixed(const EncodeArgs& a, hipStream_t s);
-bool rs_encode23_applies(uint32_t k, uint32_t m);            // fec_encode23.hip
+// Which of them a pass of m parity rows takes, decided from the code's own matrix: its kind
+// (FEC_MATRIX_*; the bit-sliced networks are generated per kind, gen_bitslice.py) and its parity rows
+// `prows` (m x k; RS(2,3) runs fec_encode23.hip only with the row 03 02). none: the generic kernel.
+enum class FixedEncode { none, rs23, dyadic84, bits };
+FixedEncode fixed_encode(uint32_t k, uint32_t m, bool dyadic, int kind, const uint8_t* prows);
+hipError_t launch_rs_encode_fixed(const EncodeArgs& a, FixedEncode which, int kind, hipStream_t s);
+bool rs_encode23_applies(uint32_t k, uint32_t m, const uint8_t* prows);   // fec_encode23.hip
 hipError_t launch_rs_encode23(const EncodeArgs& a, hipStream_t s);
 hipError_t launch_rs_plan(const PlanArgs& a, hipStream_t s);
 // Sorted plans (fec_plan.hip): lanes of a wave cooperate on one block's plan; within each

@@ -38,14 +38,19 @@ GF_HD inline uint8_t locate_multi_inv_slow(uint8_t a) {
     return r;
 }
 
-// The code's m x m coefficients, row l column i: u_{k+i} (k+i)^l.
-GF_HD inline void locate_multi_table(uint8_t* A, uint32_t k, uint32_t m) {
+// The code's m x m coefficients, row l column i: u_{k+i} (k+i)^l. logv (null: all zero, the default
+// matrix) holds log v_r for the n shards of a code whose shard r is v_r p(r) (rs_matrix.hpp grs_logv):
+// then c_r / v_r takes the place of c_r in the sums above, the coefficients are
+// (u_{k+i} / v_{k+i}) (k+i)^l, and a corrupt shard's error value is rescaled by the nonzero 1 / v_r:
+// the locator, its recurrence and its roots are the same.
+GF_HD inline void locate_multi_table(uint8_t* A, uint32_t k, uint32_t m, const uint8_t* logv = nullptr) {
     const uint32_t n = k + m;
     for (uint32_t i = 0; i < m; ++i) {
         const uint32_t r = k + i;
         uint8_t prod = 1;
         for (uint32_t j = 0; j < n; ++j)
             if (j != r) prod = gf::mul_slow(prod, (uint8_t)(r ^ j));
+        if (logv) prod = gf::mul_slow(prod, gf::kTables.exp[logv[r]]);   // u_r / v_r = 1 / (prod * v_r)
         uint8_t c = locate_multi_inv_slow(prod);   // u_r; then u_r r^l
         for (uint32_t l = 0; l < m; ++l) A[l * m + i] = c, c = gf::mul_slow(c, (uint8_t)r);
     }

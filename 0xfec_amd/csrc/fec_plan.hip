@@ -249,7 +249,8 @@ __global__ __launch_bounds__(kPlanSortThreads) void rs_plan_sorted_kernel(PlanAr
                     const uint32_t t = q < k ? S[q] : O[q - k];
                     uint32_t s = 0;
                     for (uint32_t u = 0; u < ny; ++u) s += s_l32[t ^ Y[u]];
-                    if (comp) s = s_dall[t] + 255u * 32u - s;
+                    if (comp) s = s_dall[t] + 255u * 32u - s;   // (dall holds logv[t] already)
+                    else if (a.logv) s += a.logv[t];            // direct sums: PlanArgs::logv
                     Dt[q] = (uint8_t)(s % 255u);
                 }
             }

@@ -1048,4 +1048,192 @@ int fec__selftest_wide_plan(void) {
     return 0;
 }
 
+// Internal self-test (not part of the public ABI, no device needed): the Cauchy matrix (rs_matrix.hpp
+// build_cauchy_matrix) through the arithmetic the decode plans and the locate family run with its
+// log v table (grs_logv).
+// Plans, per shape 48 seeded recoverable masks plus all parity lost and, where m >= k, all data lost:
+// with T = M[O] * inverse(rows S of M) by rs::invert, S the first k present shards and O every missing
+// shard, data and parity,
+//   - the narrow plan's sums as rs_plan_kernel forms them (D_p and N_r direct over S, + log v) and as
+//     the sorted plans form them where n - k < k (dall, which holds log v, minus the others), n <= 32;
+//   - the reconstruct-some record (some_wide_plan_record with logv);
+//   - the wide plan's rows (wide_logsum with logv, wide_coef)
+// must all give T; and without logv the record must differ from T somewhere (the table is needed).
+// Locate, per shape with 1 <= m <= 16 and per max_bad: t <= T corrupt shards (shard 0 and a parity
+// shard among them in turn) in every byte of a chunk, syndromes under the Cauchy rows; the column
+// solver over locate_multi_table(logv) must return exactly the planted set, and with e missing shards
+// (taken as zeros, rows scaled by locate_partial_scale) and t <= (m - e) / 2 likewise. 0 on success,
+// else 100000 * part + 1000 * (shape index + 1) + case index + 1.
+int fec__selftest_cauchy(void) {
+    uint8_t ex768[768];
+    for (uint32_t i = 0; i < 768; ++i) ex768[i] = fk::wide_exp768(i);
+    const uint8_t* lg = gf::kTables.log;
+    uint64_t seed = 0xC2B2AE3D27D4EB4Full;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    auto nzbyte = [&rnd]() -> uint8_t { return (uint8_t)(1 + rnd() % 255); };
+    {   // the matrix itself: identity on top, 1 / (r ^ c) below; kind 0 is build_matrix
+        const std::vector<uint8_t> M = rs::build_matrix_kind(rs::kMatrixCauchy, 8, 12);
+        static const uint8_t row0[8] = {0xad, 0x9d, 0xdd, 0x98, 0x3d, 0xaa, 0x5d, 0x96};
+        if (M.size() != 96 || memcmp(&M[64], row0, 8)) return 1;
+        for (int r = 0; r < 8; ++r)
+            for (int c = 0; c < 8; ++c)
+                if (M[(size_t)r * 8 + c] != (r == c)) return 2;
+        if (rs::build_matrix_kind(rs::kMatrixVandermonde, 8, 12) != rs::build_matrix(8, 12)) return 3;
+        if (!rs::build_matrix_kind(2, 8, 12).empty()) return 4;
+    }
+    static const int shapes[][2] = {{8, 4}, {2, 1}, {5, 3}, {20, 10}, {16, 8}, {1, 3}, {4, 8}, {3, 29},
+                                    {33, 7}, {100, 20}, {100, 156}, {128, 128}};
+    int si = 0;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix_kind(rs::kMatrixCauchy, (int)k, (int)n);
+        const std::vector<uint8_t> lv = rs::grs_logv(rs::kMatrixCauchy, (int)k, (int)n);
+        if (M.empty() || lv.size() != n) return 100000 + 1000 * si;
+        const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
+        std::vector<uint8_t> rec(lay.stride);
+        std::vector<uint32_t> dall(n);   // as get_code builds it (fec_capi.cpp)
+        for (uint32_t s = 0; s < n; ++s) {
+            uint32_t d = lv[s];
+            for (uint32_t t = 0; t < n; ++t)
+                if (t != s) d += lg[s ^ t];
+            dall[s] = d % 255u;
+        }
+        bool needed = false;
+        const int cases = 48 + 1 + (m >= k ? 1 : 0);
+        for (int ci = 0; ci < cases; ++ci) {
+            const int fail = 100000 + 1000 * si + ci + 1;
+            constexpr uint32_t W = fk::kWideMaskWords;
+            std::array<uint32_t, W> pres{};
+            std::vector<uint8_t> has(n, 1);
+            if (ci == 48) {
+                for (uint32_t i = k; i < n; ++i) has[i] = 0;
+            } else if (ci == 49) {
+                for (uint32_t i = 0; i < k; ++i) has[i] = 0;
+            } else {
+                for (uint32_t lose = 1 + rnd() % m; lose > 0;) {
+                    const uint32_t i = rnd() % n;
+                    if (has[i]) has[i] = 0, --lose;
+                }
+            }
+            std::vector<uint8_t> S, O, X;   // inputs, missing, the n - k shards that are no input
+            for (uint32_t i = 0; i < n; ++i) {
+                if (has[i]) pres[i >> 5] |= 1u << (i & 31u);
+                if (has[i] && S.size() < k) S.push_back((uint8_t)i);
+                else X.push_back((uint8_t)i);
+                if (!has[i]) O.push_back((uint8_t)i);
+            }
+            std::vector<uint8_t> inv((size_t)k * k);
+            for (uint32_t p = 0; p < k; ++p) memcpy(&inv[(size_t)p * k], &M[(size_t)S[p] * k], k);
+            if (!rs::invert((int)k, inv.data())) return fail;
+            std::vector<uint8_t> T(O.size() * k, 0);
+            for (size_t r = 0; r < O.size(); ++r)
+                for (uint32_t p = 0; p < k; ++p)
+                    for (uint32_t t = 0; t < k; ++t)
+                        T[r * k + p] ^= gf::mul(M[(size_t)O[r] * k + t], inv[(size_t)t * k + p]);
+            // reconstruct-some's record, with the table and without it
+            if (fk::some_wide_plan_record(rec.data(), lay, pres.data(), nullptr, k, n, ex768, lg, lv.data()) != 0 ||
+                rec[lay.nout_off] != O.size() || memcmp(&rec[lay.coef_off], T.data(), T.size()))
+                return fail;
+            (void)fk::some_wide_plan_record(rec.data(), lay, pres.data(), nullptr, k, n, ex768, lg);
+            needed = needed || memcmp(&rec[lay.coef_off], T.data(), T.size()) != 0;
+            // the wide plan's rows
+            std::vector<uint32_t> D(k);
+            for (uint32_t p = 0; p < k; ++p) D[p] = fk::wide_logsum(lg, S.data(), k, S[p], p, lv.data());
+            for (size_t r = 0; r < O.size(); ++r) {
+                const uint32_t N = fk::wide_logsum(lg, S.data(), k, O[r], k, lv.data());
+                for (uint32_t p = 0; p < k; ++p)
+                    if (fk::wide_coef(ex768, lg, N, D[p], O[r], S[p]) != T[r * k + p]) return fail;
+            }
+            if (n > FEC_MAX_DECODE_SHARDS) continue;
+            // the narrow plans: rs_plan_kernel's direct sums, and the sorted plans' complement sums
+            const bool comp = n - k < k;
+            for (int form = 0; form < (comp ? 2 : 1); ++form) {
+                auto sum = [&](uint32_t t) -> uint32_t {
+                    uint32_t s = 0;
+                    if (form == 0) {
+                        for (uint32_t q = 0; q < k; ++q) s += t != S[q] ? lg[t ^ S[q]] : 0u;   // (t itself: no term)
+                        return (s + lv[t]) % 255u;
+                    }
+                    for (uint32_t u = 0; u < n - k; ++u) s += t != X[u] ? lg[t ^ X[u]] : 0u;
+                    return (dall[t] + 255u * 32u - s) % 255u;
+                };
+                for (size_t r = 0; r < O.size(); ++r) {
+                    const uint32_t Nr = sum(O[r]);
+                    for (uint32_t p = 0; p < k; ++p) {
+                        const uint32_t v = Nr + 2u * 255u - lg[O[r] ^ S[p]] - sum(S[p]);
+                        if (gf::kTables.exp[v % 255u] != T[r * k + p]) return fail;
+                    }
+                }
+            }
+        }
+        if (!needed && k > 1) return 100000 + 1000 * si + 999;
+    }
+
+    // the locate family's column solver over Cauchy syndromes
+    constexpr int R = fk::kLocateMultiRows;
+    constexpr uint32_t NW = fk::kLocateMultiWords;
+    const uint8_t* ft = reinterpret_cast<const uint8_t*>(&gf::kTables);
+    static const int lshapes[][2] = {{8, 4}, {20, 10}, {64, 16}, {2, 2}, {1, 8}, {240, 16}, {3, 5}};
+    si = 0;
+    for (auto& sh : lshapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> M = rs::build_matrix_kind(rs::kMatrixCauchy, (int)k, (int)n);
+        const std::vector<uint8_t> lv = rs::grs_logv(rs::kMatrixCauchy, (int)k, (int)n);
+        const uint8_t* P = M.data() + (size_t)k * k;
+        uint8_t loctab[fk::kLocateTabBytes];
+        if (!fk::locate_table(loctab, P, k, m)) return 200000 + 1000 * si;   // the single-shard call's table
+        uint8_t A[R * R] = {};
+        fk::locate_multi_table(A, k, m, lv.data());
+        std::vector<gf::PermTab> At((size_t)m * m);
+        for (size_t i = 0; i < At.size(); ++i) At[i] = gf::make_permtab(A[i]);
+        auto col = [&](uint32_t r, uint32_t i) -> uint8_t { return r < k ? P[i * k + r] : (uint8_t)(r - k == i); };
+        for (int ci = 0; ci < 96; ++ci) {
+            const int fail = 200000 + 1000 * si + ci + 1;
+            std::vector<uint32_t> perm(n);
+            for (uint32_t r = 0; r < n; ++r) perm[r] = r;
+            for (uint32_t r = 0; r + 1 < n; ++r) std::swap(perm[r], perm[r + rnd() % (n - r)]);
+            // e missing shards first (none in the first half of the cases), then t corrupt ones
+            const uint32_t e = ci < 48 ? 0 : (ci & 1) ? std::min(1u, m) : m / 2;
+            const uint32_t sums = m - e, T = sums / 2 > (uint32_t)fk::kLocateMaxBad ? fk::kLocateMaxBad : sums / 2;
+            const uint32_t t = (ci & 2) ? T : std::min(1u, T);
+            if (t == 0) continue;   // (the solver is given columns with a nonzero sum only)
+            if (ci % 3 == 1) std::swap(perm[e], *std::find(perm.begin(), perm.end(), 0u));       // shard 0 corrupt
+            if (ci % 3 == 2) std::swap(perm[e], *std::find(perm.begin(), perm.end(), n - 1));   // a parity shard
+            uint32_t mask[NW] = {}, hitset[NW] = {};
+            for (uint32_t i = e; i < n; ++i) mask[perm[i] >> 5] |= 1u << (perm[i] & 31u);
+            // a codeword's syndromes are zero: those of the word are its differences' (missing shards read
+            // as zeros differ by the shard itself, random here)
+            uint32_t acc[R][4] = {};
+            uint8_t* S = reinterpret_cast<uint8_t*>(acc);
+            for (uint32_t j = 0; j < e + t; ++j) {
+                const uint32_t r = perm[j];
+                if (j >= e) hitset[r >> 5] |= 1u << (r & 31u);
+                for (uint32_t x = 0; x < 16; ++x) {
+                    const uint8_t v = nzbyte();
+                    for (uint32_t i = 0; i < m; ++i) S[i * 16 + x] ^= gf::mul(col(r, i), v);
+                }
+            }
+            uint32_t sup[NW] = {};
+            bool unknown;
+            if (e == 0) {
+                unknown = fk::locate_multi_chunk<R>(acc, m, n, T, At.data(), ft, sup);
+            } else {
+                gf::PermTab Lt[R] = {};
+                for (uint32_t i = 0; i < m; ++i) Lt[i] = gf::make_permtab_fast(fk::locate_partial_scale(mask, k, n, i));
+                fk::locate_partial_scale_rows<R>(acc, m, Lt);
+                unknown = fk::locate_multi_chunk<R, true>(acc, m, n, T, At.data(), ft, sup, sums, mask);
+            }
+            if (unknown || memcmp(sup, hitset, sizeof(sup)) != 0) return fail;
+        }
+    }
+    return 0;
+}
+
 }  // extern "C"

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(kSomePlanThreads) void rs_plan_some_kernel(SomePlan
     if (b < a.nblocks) {
         const uint32_t want = a.want ? a.want[b] : 0xFFFFFFFFu;
         const int32_t st = some_plan_record(recs + (size_t)threadIdx.x * lay.stride, lay, a.masks[b], want, a.k, a.n,
-                                            s_exp, s_log);
+                                            s_exp, s_log, a.logv);
         if (st) wave_flag(a.err, kStickyTooFew);   // too few shards, as rs_plan_kernel reports it
         if (a.status) a.status[b] = st;
     }

@@ -32,7 +32,7 @@ GF_HD inline uint32_t mask_bit(const uint32_t* w, uint32_t i) { return (w[i >> 5
 // ex768: wide_exp768(0..767); lg: the field's log table. n <= 256.
 GF_HD inline int32_t some_wide_plan_record(uint8_t* P, const WideLayout& lay, const uint32_t* present,
                                            const uint32_t* want, uint32_t k, uint32_t n, const uint8_t* ex768,
-                                           const uint8_t* lg) {
+                                           const uint8_t* lg, const uint8_t* logv = nullptr) {
     P[lay.nout_off] = 0;
     uint8_t* S = P + lay.in_off;
     uint8_t* O = P + lay.out_off;
@@ -55,10 +55,10 @@ GF_HD inline int32_t some_wide_plan_record(uint8_t* P, const WideLayout& lay, co
     // D_p waits in row 0 of the coefficients; rows go high to low, so row 0 replaces each D_p right
     // after reading it (as rs_plan_kernel, fec_decode.hip)
     uint8_t* C = P + lay.coef_off;
-    for (uint32_t p = 0; p < k; ++p) C[p] = (uint8_t)wide_logsum(lg, S, k, S[p], p);
+    for (uint32_t p = 0; p < k; ++p) C[p] = (uint8_t)wide_logsum(lg, S, k, S[p], p, logv);
     for (uint32_t r = e; r-- > 0;) {
         const uint32_t o = O[r];
-        const uint32_t N = wide_logsum(lg, S, k, o, k);
+        const uint32_t N = wide_logsum(lg, S, k, o, k, logv);
         for (uint32_t p = 0; p < k; ++p) C[r * k + p] = wide_coef(ex768, lg, N, C[p], o, S[p]);
     }
     P[lay.nout_off] = (uint8_t)e;
@@ -67,8 +67,9 @@ GF_HD inline int32_t some_wide_plan_record(uint8_t* P, const WideLayout& lay, co
 
 // The one-word form (k + m <= 32), which rs_plan_some_kernel runs.
 GF_HD inline int32_t some_plan_record(uint8_t* P, const WideLayout& lay, uint32_t present, uint32_t want,
-                                      uint32_t k, uint32_t n, const uint8_t* ex768, const uint8_t* lg) {
-    return some_wide_plan_record(P, lay, &present, &want, k, n, ex768, lg);
+                                      uint32_t k, uint32_t n, const uint8_t* ex768, const uint8_t* lg,
+                                      const uint8_t* logv = nullptr) {
+    return some_wide_plan_record(P, lay, &present, &want, k, n, ex768, lg, logv);
 }
 
 struct SomePlanArgs {
@@ -79,6 +80,7 @@ struct SomePlanArgs {
     int* err;                  // sticky error word
     uint32_t k, n, nblocks;
     WideLayout lay;
+    const uint8_t* logv;       // n bytes, log v_r per shard (PlanArgs::logv); null for the default matrix
 };
 
 hipError_t launch_rs_plan_some(const SomePlanArgs& a, hipStream_t s);

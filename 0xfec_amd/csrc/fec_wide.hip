@@ -91,8 +91,8 @@ __global__ __launch_bounds__(kThreads) void rs_plan_wide_kernel(WidePlanArgs a) 
     if (nout == 0) return;
     const uint8_t* S = W.hdr + lay.in_off;
     const uint8_t* O = W.hdr + lay.out_off;
-    for (uint32_t p = lane; p < k; p += 64) W.D[p] = (uint8_t)wide_logsum(s_log, S, k, S[p], p);
-    for (uint32_t r = lane; r < nout; r += 64) W.N[r] = (uint8_t)wide_logsum(s_log, S, k, O[r], k);
+    for (uint32_t p = lane; p < k; p += 64) W.D[p] = (uint8_t)wide_logsum(s_log, S, k, S[p], p, a.logv);
+    for (uint32_t r = lane; r < nout; r += 64) W.N[r] = (uint8_t)wide_logsum(s_log, S, k, O[r], k, a.logv);
     wave_sync();
     const uint32_t tot = nout * k;   // the record holds rows * k >= tot bytes, rounded up to 16
     uint32_t* C = reinterpret_cast<uint32_t*>(rec + lay.coef_off);

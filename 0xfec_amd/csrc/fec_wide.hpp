@@ -45,9 +45,12 @@ constexpr uint32_t kWideHdrMax = 272;
 GF_HD inline uint8_t wide_exp768(uint32_t i) { return gf::kTables.exp[i % 255u]; }
 
 // sum over q < k, q != skip of log(x ^ S[q]), mod 255 (skip >= k: every q). x ^ S[q] is nonzero
-// for every term taken: the shard indices are distinct.
-GF_HD inline uint32_t wide_logsum(const uint8_t* lg, const uint8_t* S, uint32_t k, uint32_t x, uint32_t skip) {
-    uint32_t d = 0;
+// for every term taken: the shard indices are distinct. logv (null: the default matrix) adds log v_x,
+// the multiplier of shard x in a code whose shard r is v_r p(r) (rs_matrix.hpp grs_logv): D_p and N_r
+// each take their own shard's, and wide_coef below is then exp(N_o + log v_o - log(o ^ s) - D_s - log v_s).
+GF_HD inline uint32_t wide_logsum(const uint8_t* lg, const uint8_t* S, uint32_t k, uint32_t x, uint32_t skip,
+                                  const uint8_t* logv = nullptr) {
+    uint32_t d = logv ? logv[x] : 0u;
     for (uint32_t q = 0; q < k; ++q)
         if (q != skip) d += lg[x ^ S[q]];
     return d % 255u;
@@ -74,6 +77,7 @@ struct WidePlanArgs {
     uint32_t max_out;          // recover: output slots per block (0: in place)
     WideLayout lay;
     FastDiv div_k;
+    const uint8_t* logv;       // n bytes, log v_r per shard (PlanArgs::logv); null for the default matrix
 };
 
 // A workgroup rebuilds a tile of g consecutive blocks x c consecutive chunks (g * c <= 256, one

@@ -64,4 +64,44 @@ inline std::vector<uint8_t> build_matrix(int k, int n) {
     return out;
 }
 
+// The matrix kinds of fec_hip_matrix.h (FEC_MATRIX_*).
+constexpr int kMatrixVandermonde = 0, kMatrixCauchy = 1, kMatrixKinds = 2;
+
+// klauspost WithCauchyMatrix (ISA-L gf_gen_cauchy1_matrix over the same field): identity on top,
+// M[r][c] = 1 / (r ^ c) for r >= k. Every square submatrix of a Cauchy matrix is invertible, so any
+// k rows of M are independent. Empty on failure.
+inline std::vector<uint8_t> build_cauchy_matrix(int k, int n) {
+    std::vector<uint8_t> out;
+    if (k <= 0 || n < k || n > 256) return out;
+    out.assign((size_t)n * k, 0);
+    for (int r = 0; r < k; ++r) out[(size_t)r * k + r] = 1;
+    for (int r = k; r < n; ++r)
+        for (int c = 0; c < k; ++c) out[(size_t)r * k + c] = gf::inv((uint8_t)(r ^ c));
+    return out;
+}
+
+// The n x k systematic matrix of a kind; empty on failure (an unknown kind among them).
+inline std::vector<uint8_t> build_matrix_kind(int kind, int k, int n) {
+    if (kind == kMatrixVandermonde) return build_matrix(k, n);
+    if (kind == kMatrixCauchy) return build_cauchy_matrix(k, n);
+    return {};
+}
+
+// Both kinds are generalized Reed-Solomon codes on the points 0 .. n-1: shard r of a consistent block
+// is v_r p(r) for one polynomial p of degree < k. The default code has v = 1. For the Cauchy code,
+// interpolating x_c / v_c at the data points and evaluating at r >= k gives
+// prod_{t<k} (r ^ t) * sum_c x_c / (r ^ c), so v_r = 1 / prod_{c<k, c != r} (r ^ c) for every r.
+// Returns log v_r mod 255 for r < n: all a decode plan or a locate table needs beyond the points.
+inline std::vector<uint8_t> grs_logv(int kind, int k, int n) {
+    std::vector<uint8_t> lv((size_t)n, 0);
+    if (kind != kMatrixCauchy) return lv;
+    for (int r = 0; r < n; ++r) {
+        unsigned s = 0;
+        for (int c = 0; c < k; ++c)
+            if (c != r) s += gf::kTables.log[r ^ c];
+        lv[(size_t)r] = (uint8_t)((255u - s % 255u) % 255u);
+    }
+    return lv;
+}
+
 }  // namespace rs

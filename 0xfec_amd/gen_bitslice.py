@@ -24,6 +24,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "csrc", "fec_bitslice.inc")
 SHAPES = ((8, 4, 4), (16, 8, 4), (20, 10, 4))   # (k, m, group size G)
+# The same for klauspost's WithCauchyMatrix (cauchy_parity_rows), kind 1 of fec_hip_matrix.h: networks
+# of their own for the two shapes that run bit-sliced (Cauchy RS(8,12) is dyadic like the default one
+# and runs the dyadic kernel from its own leaf tables).
+CAUCHY_SHAPES = ((16, 8, 4), (20, 10, 4))
+KIND_DEFAULT, KIND_CAUCHY = 0, 1
 
 # ---------------------------------------------------------------- GF(2^8), poly 0x11D, generator 2
 _EXP = [0] * 512
@@ -77,6 +82,11 @@ def parity_rows(k, m):
     return [[_dot(v[r], [top[i][c] for i in range(k)]) for c in range(k)] for r in range(k, n)]
 
 
+def cauchy_parity_rows(k, m):
+    """klauspost WithCauchyMatrix (ISA-L gf_gen_cauchy1_matrix): M[r][c] = 1 / (r ^ c); rows k..n-1."""
+    return [[ginv(r ^ c) for c in range(k)] for r in range(k, k + m)]
+
+
 def _dot(x, y):
     s = 0
     for a, b in zip(x, y):
@@ -84,9 +94,10 @@ def _dot(x, y):
     return s
 
 
-def bit_matrix(k, m):
-    """rows[8r + b] = the set of input planes 8j + i whose XOR is bit plane b of parity r."""
-    rows = parity_rows(k, m)
+def bit_matrix(k, m, rows=None):
+    """rows[8r + b] = the set of input planes 8j + i whose XOR is bit plane b of parity r
+    (rows: the m parity rows; None: parity_rows(k, m))."""
+    rows = parity_rows(k, m) if rows is None else rows
     out = []
     for r in range(m):
         for b in range(8):
@@ -128,11 +139,12 @@ def _paar(rows, first_var):
     return pairs, rows
 
 
-def schedule(k, m, g, temp_base=None):
+def schedule(k, m, g, temp_base=None, rows=None):
     """The network as ops over variables: 0..8k-1 are the input planes (8j + i); temporaries
     follow (from temp_base). Ops: ("t", v, a, b, group)  v = a ^ b;  ("acc", r, terms, group)
-    y[r] ^= XOR(terms) (the first acc of a row assigns). Rows r = 8 * parity + bit."""
-    full = bit_matrix(k, m)
+    y[r] ^= XOR(terms) (the first acc of a row assigns). Rows r = 8 * parity + bit.
+    rows: the code's m parity rows (None: parity_rows(k, m), the default matrix)."""
+    full = bit_matrix(k, m, rows)
     ops = []
     nxt = 8 * k if temp_base is None else temp_base
     for gi, s0 in enumerate(range(0, k, g)):
@@ -178,18 +190,22 @@ def _name(v, g):
     return "x[%d][%d]" % (v // 8 % g, v % 8) if v < 8 * 256 else "t%d" % (v - 8 * 256)
 
 
-def emit_fn(k, m, g):
-    """One device function per group of g shards: bs_grp<k, m, group>(x, y), x the group's planes."""
-    ops = schedule(k, m, g, temp_base=8 * 256)
-    out = ["// RS(%d,%d): %d input planes -> %d parity planes, groups of %d shards, %d VALU ops per"
-           % (k, k + m, 8 * k, 8 * m, g, op_count(ops)),
-           "// 32-byte column (a dense bit matrix has %d ones)." % sum(len(r) for r in bit_matrix(k, m))]
-    out += ["template <>", "struct BsShape<%d, %d> {" % (k, m), "    static constexpr int G = %d;" % g, "};"]
+def emit_fn(k, m, g, kind=KIND_DEFAULT):
+    """One device function per group of g shards: bs_grp<k, m, group>(x, y), x the group's planes.
+    The default matrix's are emitted as they always were (the templates' kind defaults to 0); the
+    Cauchy ones carry the kind tag: BsShape<k, m, 1>, bs_grp<k, m, group, 1>."""
+    rows = cauchy_parity_rows(k, m) if kind == KIND_CAUCHY else None
+    tag = ", %d" % kind if kind else ""
+    ops = schedule(k, m, g, temp_base=8 * 256, rows=rows)
+    out = ["// %sRS(%d,%d): %d input planes -> %d parity planes, groups of %d shards, %d VALU ops per"
+           % ("Cauchy " if kind == KIND_CAUCHY else "", k, k + m, 8 * k, 8 * m, g, op_count(ops)),
+           "// 32-byte column (a dense bit matrix has %d ones)." % sum(len(r) for r in bit_matrix(k, m, rows))]
+    out += ["template <>", "struct BsShape<%d, %d%s> {" % (k, m, tag), "    static constexpr int G = %d;" % g, "};"]
     seen = set()
     for gi in range((k + g - 1) // g):
         lines = ["template <>",
-                 "__device__ __forceinline__ void bs_grp<%d, %d, %d>(const uint32_t (&x)[%d][8], uint32_t (&y)[%d][8]) {"
-                 % (k, m, gi, g, m)]
+                 "__device__ __forceinline__ void bs_grp<%d, %d, %d%s>(const uint32_t (&x)[%d][8], uint32_t (&y)[%d][8]) {"
+                 % (k, m, gi, tag, g, m)]
         for op in ops:
             if op[-1] != gi:
                 continue
@@ -218,8 +234,10 @@ def render():
     head = ("// fec_bitslice.inc — GENERATED by 0xfec_amd/gen_bitslice.py; do not edit.\n"
             "// Bit-sliced XOR networks of klauspost's systematic RS parity rows (reed_solomon.go:51\n"
             "// Encode), included by fec_encode.hip. bs_grp<k, m, group>: x[j][b] = bit plane b of data shard\n"
-            "// group * G + j; y[r][b] = bit plane b of parity shard r.\n\n")
-    return head + "\n".join(emit_fn(k, m, g) for k, m, g in SHAPES)
+            "// group * G + j; y[r][b] = bit plane b of parity shard r. The networks of the default matrix come\n"
+            "// first; those of the Cauchy matrix (kind 1) follow, tagged with their kind.\n\n")
+    return head + "\n".join([emit_fn(k, m, g) for k, m, g in SHAPES] +
+                            [emit_fn(k, m, g, KIND_CAUCHY) for k, m, g in CAUCHY_SHAPES])
 
 
 def main():
@@ -235,6 +253,8 @@ def main():
         f.write(text)
     for k, m, g in SHAPES:
         print("RS(%d,%d): %d ops" % (k, k + m, op_count(schedule(k, m, g))))
+    for k, m, g in CAUCHY_SHAPES:
+        print("Cauchy RS(%d,%d): %d ops" % (k, k + m, op_count(schedule(k, m, g, rows=cauchy_parity_rows(k, m)))))
 
 
 if __name__ == "__main__":
