@@ -34,14 +34,25 @@ odd), shard 0 and a parity shard first, every byte of their slots garbage; a cla
 radius of 2 by having one missing shard, and in 256 shards class a keeps to 1 and 2 missing shards
 (see there). At most two corrupt byte columns per block. The bytes depend on (call, code, L, max_bad)
 alone, not on the layout, so the model's work is done once per batch.
+
+Every piece takes an optional vector v of per-shard multipliers (cauchy_oracle.multipliers) for a code
+whose shard r is v_r p(r), the Cauchy code: the model decodes y_r / v_r, the weights are u_r / v_r (so
+the zero pivots and the pseudo-roots are those of that code; the bytes of a batch built for u_r are
+ordinary errors to it), class b's codeword is v_r g prod (r ^ j), a located class a block heals to
+v_r f(r), and the clean codewords come from the encoder given as `oracle` (cauchy_oracle). Without v
+nothing changes: the same draws, bytes and expectations as before. The Cauchy batches: CAUCHY_CODES x
+CAUCHY_LENS (params(cauchy=True)).
 """
 import numpy as np
 
 from arena import CANARY, oracle_arena, place, shards  # noqa: F401
-from locate_model import UNKNOWN, model_block, plan, poly_eval, reduce_rows, xdot
+from locate_model import UNKNOWN, model_block, plan, poly_eval, reduce_rows, unscale, xdot
 
 CODES = [(8, 4), (20, 10), (20, 9), (4, 16), (40, 16), (240, 16)]
 LENS = [17, 33, 1202]
+# under the Cauchy code: k a power of two and not, m odd, more than 32 shards, 256 shards
+CAUCHY_CODES = [(8, 4), (20, 9), (40, 16), (240, 16)]
+CAUCHY_LENS = [33, 1202]
 CYCLE = ["a", "b", "c", "d", "e", "f", "loc"]
 MODEL = "model"      # a column whose expectation is the model's
 
@@ -69,7 +80,7 @@ class Col:
 class Builder:
     """The constructions for one set of present shards."""
 
-    def __init__(self, gf, k, n, P, T, rng):
+    def __init__(self, gf, k, n, P, T, rng, v=None):
         self.mul, self.inv = gf[0].astype(np.int64), gf[1].astype(np.int64)
         self.gf, self.k, self.n, self.P, self.T, self.rng = gf, k, n, sorted(P), T, rng
         self.ms = len(self.P) - k
@@ -78,6 +89,9 @@ class Builder:
         if key not in _U:
             _U[key] = {r: int(self.inv[self.prod(r ^ j for j in self.P if j != r)]) for r in self.P}
         self.u = _U[key]
+        self.v = None if v is None else [int(x) for x in v]
+        if v is not None:       # shard r = v_r p(r): an error e_r there is e_r / v_r in p's values
+            self.u = {r: int(self.mul[u, self.inv[self.v[r]]]) for r, u in self.u.items()}
 
     def prod(self, xs):
         p = 1
@@ -127,6 +141,8 @@ class Builder:
         A, g = S[Tp:], self.nz()
         rest = [j for j in self.P if j not in S]
         cw = [int(self.mul[g, self.prod(r ^ j for j in rest)]) for r in range(self.n)]
+        if self.v is not None:
+            cw = [int(self.mul[self.v[r], c]) for r, c in enumerate(cw)]
         assert all((cw[r] != 0) == (r in S) for r in self.P)
         return Col({r: cw[r] for r in A}, frozenset(S[:Tp]), cw)
 
@@ -174,9 +190,9 @@ class Builder:
 class Cases:
     """A batch of hard blocks for one (call, code, L, max_bad); the same bytes in every layout."""
 
-    def __init__(self, oracle, gf, call, k, m, L, max_bad):
+    def __init__(self, oracle, gf, call, k, m, L, max_bad, mult=None):
         assert call in ("multi", "partial")
-        self.oracle, self.gf, self.call = oracle, gf, call
+        self.oracle, self.gf, self.call, self.mult = oracle, gf, call, mult
         self.k, self.m, self.n, self.L, self.max_bad = k, m, k + m, L, max_bad
         self.B = B = nblocks(k, m)
         n = k + m
@@ -206,7 +222,7 @@ class Cases:
             miss = self.erasures(e) if e else set()
             P = sorted(set(range(n)) - miss)
             T = min(max_bad, (len(P) - k) // 2)
-            bd = Builder(gf, k, n, P, T, rng)
+            bd = Builder(gf, k, n, P, T, rng, mult)
             if kind == "d" and not miss:
                 kind = "a"
             if kind == "e" and T < 2:
@@ -274,13 +290,15 @@ class Cases:
         self.want = np.zeros(B, dtype=np.int32)
         self.sets = [frozenset()] * B
         for b in range(B):
-            self.want[b], self.sets[b] = model_block(gf, k, m, set(range(n)) - self.miss[b], self.bad[b], L, max_bad)
+            self.want[b], self.sets[b] = model_block(gf, k, m, set(range(n)) - self.miss[b], self.bad[b], L, max_bad, mult)
             if self.built[b] is None and self.want[b] > 0:
                 # a class a block that ends located heals to the codeword through the other present shards
                 rest = sorted(set(range(n)) - self.miss[b] - self.sets[b])
                 for x in self.cols[b]:
-                    f = xdot(gf[0], plan(gf, rest, k)[0], self.bad[b][rest, x][:, None])[:, 0]
+                    f = xdot(gf[0], plan(gf, rest, k)[0], unscale(gf, rest, self.bad[b][rest, x], mult)[:, None])[:, 0]
                     self.final[b, :, x] = poly_eval(gf, f, range(n))
+                    if mult is not None:
+                        self.final[b, :, x] = gf[0][np.asarray(mult, dtype=np.uint8), self.final[b, :, x]]
         self.final.setflags(write=False)
 
     def erasures(self, e):
@@ -316,14 +334,17 @@ class Cases:
         return img, clean, data, par
 
 
-def cases(oracle, gf, call, k, m, L, max_bad):
-    key = (call, k, m, L, max_bad)
+def cases(oracle, gf, call, k, m, L, max_bad, v=None):
+    """The batch, built once. v: the multipliers of the code that `oracle` encodes."""
+    key = (call, k, m, L, max_bad) + (() if v is None else (bytes(bytearray(int(x) for x in v)),))
     if key not in _CACHE:
-        _CACHE[key] = Cases(oracle, gf, call, k, m, L, max_bad)
+        _CACHE[key] = Cases(oracle, gf, call, k, m, L, max_bad, v)
     return _CACHE[key]
 
 
-def params():
-    """(call, k, m, L, max_bad) of every batch."""
-    return [(call, k, m, L, mb) for call in ("multi", "partial") for k, m in CODES for L in LENS
+def params(cauchy=False, lens=None):
+    """(call, k, m, L, max_bad) of every batch; cauchy: of the batches under the Cauchy code (lens: at
+    other lengths than those the device runs)."""
+    codes, lens = (CAUCHY_CODES, lens or CAUCHY_LENS) if cauchy else (CODES, lens or LENS)
+    return [(call, k, m, L, mb) for call in ("multi", "partial") for k, m in codes for L in lens
             for mb in max_bads(k, m)]

@@ -117,12 +117,24 @@ def poly_eval(gf, f, pts):
     return v
 
 
-def bw_column(gf, P, y, k, T):
+def unscale(gf, P, Y, v):
+    """Y (row i: the shard at point P[i]) with every row divided by its multiplier v[P[i]]: a codeword
+    of a generalized Reed-Solomon code, shard r = v_r p(r), becomes the values p(r). v None: Y."""
+    if v is None:
+        return Y
+    mul, inv = gf
+    scale = inv[np.asarray(v, dtype=np.uint8)[[int(r) for r in P]]]
+    assert scale.all(), "multipliers are not zero"
+    return mul[scale.reshape((-1,) + (1,) * (np.ndim(Y) - 1)), Y]
+
+
+def bw_column(gf, P, y, k, T, v=None):
     """The errors of the byte column y (y[i] at point P[i]) within T of a codeword: a frozenset of
-    points of P, or None if no codeword lies within T."""
+    points of P, or None if no codeword lies within T. v: per-shard multipliers (see unscale); the
+    column decoded is y_r / v_r, whose errors sit at the same points."""
     mul, _ = gf
     P = [int(r) for r in P]
-    y = np.asarray(y, dtype=np.uint8)
+    y = unscale(gf, P, np.asarray(y, dtype=np.uint8), v)
     assert len(P) == y.size and k + 2 * T <= len(P)
     top, null = plan(gf, P, k + T)
     A = mul[y[:, None], powers(gf, P, T + 1)]             # the E part of the system: y_r r^j
@@ -137,15 +149,15 @@ def bw_column(gf, P, y, k, T):
     return frozenset(P[i] for i in wrong) if wrong.size <= T else None
 
 
-def syndromes(gf, P, Y, k):
+def syndromes(gf, P, Y, k, v=None):
     """[|P| - k, L]: zero exactly in the byte columns of Y (row i: the shard at point P[i]) that are
-    codewords."""
-    return xdot(gf[0], plan(gf, [int(r) for r in P], k)[1], Y)
+    codewords (with multipliers v: whose rows divided by v are)."""
+    return xdot(gf[0], plan(gf, [int(r) for r in P], k)[1], unscale(gf, P, Y, v))
 
 
-def model_block(gf, k, m, present, y, L, max_bad):
-    """One block by the definition: present (the shards the caller holds), y [n, >= L] its shards.
-    Returns (result, frozenset): too few, 0, (|U|, U) or unknown."""
+def model_block(gf, k, m, present, y, L, max_bad, v=None):
+    """One block by the definition: present (the shards the caller holds), y [n, >= L] its shards, v the
+    code's multipliers (None: all one). Returns (result, frozenset): too few, 0, (|U|, U) or unknown."""
     n = k + m
     P = sorted(int(r) for r in present)
     e = n - len(P)
@@ -154,7 +166,7 @@ def model_block(gf, k, m, present, y, L, max_bad):
     if len(P) <= k:
         return 0, frozenset()
     T = min(max_bad, (m - e) // 2)
-    Y = np.ascontiguousarray(y[P, :L])
+    Y = unscale(gf, P, np.ascontiguousarray(y[P, :L]), v)
     bad = syndromes(gf, P, Y, k).any(axis=0)
     if not bad.any():
         return 0, frozenset()
@@ -168,12 +180,13 @@ def model_block(gf, k, m, present, y, L, max_bad):
     return (len(U), frozenset(U)) if len(U) <= T else (UNKNOWN, frozenset())
 
 
-def model_batch(gf, k, m, shards, L, max_bad, missing=None):
-    """(results [B] int32, sets [B]) of a batch [B, n, >= L]; missing: per block the shards not held."""
+def model_batch(gf, k, m, shards, L, max_bad, missing=None, v=None):
+    """(results [B] int32, sets [B]) of a batch [B, n, >= L]; missing: per block the shards not held;
+    v: the code's multipliers."""
     B, n = shards.shape[0], k + m
     want = np.zeros(B, dtype=np.int32)
     sets = [frozenset()] * B
     for b in range(B):
         present = set(range(n)) - set(missing[b] if missing else ())
-        want[b], sets[b] = model_block(gf, k, m, present, shards[b], L, max_bad)
+        want[b], sets[b] = model_block(gf, k, m, present, shards[b], L, max_bad, v)
     return want, sets

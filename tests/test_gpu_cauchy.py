@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import cauchy_model as cm
-from arena import torch  # noqa: F401
+import cauchy_oracle
+from arena import gf, torch  # noqa: F401
+from locate_model import UNKNOWN, model_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -610,5 +612,97 @@ def test_kind_switches_between_calls_without_a_sync(fec, torch):
         c.xor_encode(3, x)
         c.sync()
         assert np.array_equal(x.cpu().numpy()[:, 3], data[:, 0] ^ data[:, 1] ^ data[:, 2])
+    finally:
+        c.close()
+
+
+def test_kind_switches_between_queued_decode_and_locate_calls(fec, torch, oracle, gf):
+    """RS(12,17), 1202-byte shards, a fresh ctx: decode and locate calls of both kinds queued with no sync
+    in between. Each kind's code object is built inside the sequence and then used again; the plan
+    workspace is shared by all of the calls, and the tables must be those of the kind that was current at
+    each launch. The data multipliers of this code differ (1, 103, ...), so a Cauchy plan computed with
+    kind 0's tables, or the reverse, gives other bytes."""
+    rng = np.random.default_rng(1217)
+    k, m, B, L, S = 12, 5, 67, 1202, 1216
+    n, T = k + m, m // 2
+    v = cauchy_oracle.code_multipliers(k, m)
+    assert len(set(v[:k].tolist())) > 1
+    # the two prepared batches: the oracle's codewords and the Cauchy model's, of the same data
+    shC = codewords(rng, mat(k, m), B, L, S)
+    sh0 = shC.copy()
+    oracle.rs_encode(k, m, sh0)
+    assert not sh0[:, :, L:].any() and not np.array_equal(sh0[:, k:], shC[:, k:])
+    pres0 = lose(rng, B, n, rng.integers(0, m + 1, B))
+    presC = lose(rng, B, n, rng.integers(0, m + 1, B))
+    pres0[0], presC[0] = True, True
+    pres0[0, :m], presC[0, :m] = False, False          # the first data shards: every input past them
+    presC[1] = True
+    presC[1, [0, 5, k]] = False                       # data shards of both multipliers and a parity shard
+    dmg0, dmgC = damage(sh0, pres0), damage(shC, presC)
+    # the corrupted Cauchy batch: single bytes in t shards of a block, t = b % 4 (3 is past the radius: the
+    # code has distance 6, so three errors are never within 2 of another codeword)
+    bad = shC.copy()
+    hit = [sorted(int(s) for s in rng.choice(n, size=b % 4, replace=False)) for b in range(B)]
+    for b in range(B):
+        for j, s in enumerate(hit[b]):
+            bad[b, s, [0, L - 1, int(rng.integers(L))][(b + j) % 3]] ^= int(rng.integers(1, 256))
+    want4, sets4 = model_batch(gf, k, m, bad, L, 8, v=v)
+    assert [int(x) for x in want4] == [len(h) if len(h) <= T else UNKNOWN for h in hit]
+    assert all(sets4[b] == frozenset(hit[b]) for b in range(B) if len(hit[b]) <= T)
+    want7, _ = model_batch(gf, k, m, bad, L, 8)        # to kind 0 the Cauchy codewords are no codewords
+    assert (want7 == UNKNOWN).all()
+    good = np.ones((B, n), dtype=bool)
+    for b in np.flatnonzero(want4 > 0):
+        good[b, sorted(sets4[b])] = False
+
+    c = fec.Codec(0).use_torch_stream()
+    try:
+        # every buffer is on the device before the first call, so no copy waits between the calls
+        d1, d3, dbad = dev(torch, dmg0), dev(torch, dmgC), dev(torch, bad)
+        d6, p6 = dev(torch, dmg0[:, :k]), dev(torch, dmg0[:, k:])
+        mk0, mkC = i32(torch, words1(pres0)), i32(torch, words1(presC))
+        st = [torch.full((B,), 99, dtype=torch.int32, device="cuda") for _ in range(4)]
+        cnt4, cnt7 = (torch.full((B,), 99, dtype=torch.int32, device="cuda") for _ in range(2))
+        pm4, pm7 = (torch.full((B, 1), 0x5EED, dtype=torch.int32, device="cuda") for _ in range(2))
+        two4, two7 = (torch.full((2,), 9, dtype=torch.int32, device="cuda") for _ in range(2))
+        out6 = torch.full((B, m, S), STALE, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        assert c.matrix == "vandermonde"
+        c.rs_reconstruct(k, m, d1, mk0, status=st[0], shard_len=L)                              # 1
+        c.set_matrix("cauchy")                                                                  # 2
+        c.rs_reconstruct(k, m, d3, mkC, status=st[1], shard_len=L)                              # 3
+        c.rs_locate_multi(k, m, dbad, cnt4, present_out=pm4, counts=two4, shard_len=L)          # 4
+        c.set_matrix(0)                                                                         # 5
+        c.rs_recover_split(k, m, d6, p6, mk0, out6, status=st[2], shard_len=L)                  # 6
+        c.rs_locate_multi(k, m, dbad, cnt7, present_out=pm7, counts=two7, shard_len=L)          # 7
+        c.set_matrix("cauchy")                                                                  # 8
+        c.rs_reconstruct_some(k, m, dbad, pm4.reshape(B), status=st[3], shard_len=L)
+        c.sync()
+        assert c.matrix == "cauchy"
+        lost0, lostC = ~pres0, ~presC
+        lost0[:, k:], lostC[:, k:] = False, False
+        assert (st[0].cpu().numpy() == 0).all()
+        assert np.array_equal(d1.cpu().numpy(), rebuilt(dmg0, sh0, pres0, L, lost0))
+        assert (st[1].cpu().numpy() == 0).all()
+        assert np.array_equal(d3.cpu().numpy(), rebuilt(dmgC, shC, presC, L, lostC))
+        assert np.array_equal(cnt4.cpu().numpy(), want4)
+        assert np.array_equal(pm4.cpu().numpy().view(np.uint32).reshape(B), words1(good))
+        assert two4.cpu().tolist() == [int((want4 > 0).sum()), int((want4 == UNKNOWN).sum())]
+        assert np.array_equal(st[2].cpu().numpy(), lost0.sum(axis=1))
+        wout = np.full((B, m, S), STALE, dtype=np.uint8)
+        for b in range(B):
+            for r, i in enumerate(np.nonzero(lost0[b])[0]):
+                wout[b, r, :L] = sh0[b, i, :L]
+                wout[b, r, L:rup16(L)] = 0
+        assert np.array_equal(out6.cpu().numpy(), wout)
+        assert np.array_equal(d6.cpu().numpy(), dmg0[:, :k]) and np.array_equal(p6.cpu().numpy(), dmg0[:, k:])
+        got7 = cnt7.cpu().numpy()
+        assert (got7 != 0).all() and np.array_equal(got7, want7)
+        assert (pm7.cpu().numpy().view(np.uint32) == (1 << n) - 1).all() and two7.cpu().tolist() == [0, B]
+        assert (st[3].cpu().numpy() == 0).all()
+        healed = d = dbad.cpu().numpy()
+        assert np.array_equal(healed, rebuilt(bad, shC, good, L, ~good))
+        ok = want4 >= 0
+        assert ok.sum() > B // 2 and np.array_equal(d[ok], shC[ok]) and np.array_equal(d[~ok], bad[~ok])
     finally:
         c.close()

@@ -12,10 +12,17 @@ and at 8 words, and the counts. Then the heal loop, fec_rs_reconstruct_some_batc
 fec_rs_reconstruct_some_wide_batch above, with the whole arena compared again: a located block holds
 its original bytes in every shard, a miscorrected one (class b) the codeword clean ^ c, which
 fec_rs_verify_batch passes; an unknown block's present shards are untouched.
+
+The same runs under the Cauchy code (a ctx with FEC_MATRIX_CAUCHY): the batches of
+locate_hard_cases.params(cauchy=True), whose clean codewords are cauchy_oracle's and whose zero pivots,
+pseudo-roots and miscorrections are built with the weights u_r / v_r, so they are the hard cases of
+that code; fec_rs_locate_batch is held to model_verdicts over the Cauchy matrix. The codes: k a power
+of two and not, m odd, and 40 and 256 shards, which heal through rs_plan_wide_kernel<true>.
 """
 import numpy as np
 import pytest
 
+import cauchy_oracle
 from arena import STALE, check_arena, codec, gf, rup16, torch  # noqa: F401
 from locate_hard_cases import cases, params
 from locate_model import UNKNOWN
@@ -26,6 +33,14 @@ from test_gpu_locate_partial import PBatch
 pytestmark = pytest.mark.gpu
 
 LAYOUTS = ["interleaved", "split"]
+
+
+@pytest.fixture(scope="module")
+def cauchy_codec(fec):
+    c = fec.Codec(0, matrix="cauchy").use_torch_stream()
+    assert c.matrix == "cauchy"
+    yield c
+    c.close()
 
 
 class Hard:
@@ -152,3 +167,12 @@ class HardPartial(Hard, PBatch):
 def test_locate_hard_cases_and_heal(codec, torch, fec, oracle, gf, call, k, m, L, max_bad, layout):
     cs = cases(oracle, gf, call, k, m, L, max_bad)
     (HardMulti if call == "multi" else HardPartial)(codec, fec, torch, oracle, gf, cs, layout).run()
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("call,k,m,L,max_bad", params(cauchy=True))
+@pytest.mark.parametrize("matrix", ["cauchy"])
+def test_locate_hard_cases_and_heal_under(cauchy_codec, torch, fec, gf, matrix, call, k, m, L, max_bad, layout):
+    assert np.array_equal(gf[0], cauchy_oracle.gf()[0])
+    cs = cases(cauchy_oracle, gf, call, k, m, L, max_bad, cauchy_oracle.code_multipliers(k, m))
+    (HardMulti if call == "multi" else HardPartial)(cauchy_codec, fec, torch, cauchy_oracle, gf, cs, layout).run()

@@ -79,13 +79,14 @@ def model_brute(oracle, gf, k, m, T, shards, L):
     S = shards[:, k:, :L] ^ want[:, k:, :]                     # [B, m, L]
     P = oracle.build_matrix(k, k + m)[k:]                      # [m, k]
     H = np.concatenate([P, np.eye(m, dtype=np.uint8)], axis=1)  # [m, n]
+    code = P.tobytes()                                         # the cache of null spaces is per matrix
     for b in np.flatnonzero(S.reshape(B, -1).any(axis=1)):
         cols = np.unique(S[b][:, S[b].any(axis=0)], axis=1)    # the distinct nonzero syndrome columns
         counts[b] = UNKNOWN
         for v in range(1, T + 1):
             found = []
             for E in itertools.combinations(range(n), v):
-                N = left_null(gf, H[:, list(E)], (k, m, E))
+                N = left_null(gf, H[:, list(E)], (k, m, E, code))
                 if not np.bitwise_xor.reduce(mul[N[:, :, None], cols[None, :, :]], axis=1).any():
                     found.append(E)
             assert len(found) <= 1, "distance m + 1 > 2 T: at most one smallest set explains a block"

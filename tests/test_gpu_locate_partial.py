@@ -43,11 +43,12 @@ def model_brute(oracle, gf, k, m, T, present, y, L):
     """One block by the definition: present (sorted shard indices), y [n, S]. (count, frozenset)."""
     mul, _ = gf
     M = oracle.build_matrix(k, k + m)
+    code = M[k:].tobytes()                                # the cache of null spaces is per matrix
 
     def residue(rows, Y):
         """N Y for a basis N of the left null space of the generator's rows `rows`: zero columns are the
         columns of Y (one byte per row) that lie in the column space of those rows."""
-        N = left_null(gf, M[list(rows)], ("punctured", k, m, tuple(rows)))
+        N = left_null(gf, M[list(rows)], ("punctured", k, m, tuple(rows), code))
         return np.bitwise_xor.reduce(mul[N[:, :, None], Y[None, :, :]], axis=1)
     if len(present) <= k:
         return 0, frozenset()                             # any k rows of the generator are independent

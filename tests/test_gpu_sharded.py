@@ -75,7 +75,13 @@ def test_eight_ranks_in_sequence_equal_one_pass(fec, torch, shard, bench, oracle
         sh = np.zeros((48, k + m, bench.SHARD_LEN), dtype=np.uint8)
         sh[:, :k] = data[pick, :, :bench.SHARD_LEN]
         oracle.rs_encode(k, m, sh)
-        assert np.array_equal(b.parity.cpu().numpy()[pick, :, :bench.SHARD_LEN], sh[:, k:])
+        got = b.parity.cpu().numpy()[pick, :, :bench.SHARD_LEN]
+        diff = np.argwhere(got != sh[:, k:])
+        assert np.array_equal(got, sh[:, k:]), "rank %d: %d parity bytes differ from the oracle's in %d of 48 blocks; " \
+            "(pick, row, byte) %s ... %s; blocks %s; rows %s; bytes %d..%d; parity at 0x%x, data at 0x%x" % (
+                rank, len(diff), len(np.unique(diff[:, 0])), diff[0].tolist(), diff[-1].tolist(),
+                sorted(int(pick[i]) for i in np.unique(diff[:, 0]))[:12], np.unique(diff[:, 1]).tolist(),
+                diff[:, 2].min(), diff[:, 2].max(), b.parity.data_ptr(), b.data.data_ptr())
         assert st.check_full(torch)
         parts.append(b.parity.cpu().numpy())
         del b, st

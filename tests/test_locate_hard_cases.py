@@ -12,15 +12,21 @@ checked without a device:
   - a Python port of the library's column solver (fec_locate_multi.hpp: locate_multi_column) agrees with
     the model on every block, and stops agreeing on blocks of classes a, c and d when its count of roots
     or its range check is taken out: the batches can tell such a solver from a right one.
+
+All of it again for the batches under the Cauchy code (cauchy_oracle as the encoder, its multipliers
+through the model, the constructions and the port), at the two lengths the device runs and at 17; there
+a class e block's bytes, given to the model without the multipliers, do not decode to the planted set,
+and its errors are no zero pivot under the unscaled weights: the case belongs to the Cauchy weights.
 """
 import functools
 
 import numpy as np
 import pytest
 
+import cauchy_oracle
 from arena import gf, oracle_arena  # noqa: F401
-from locate_hard_cases import CODES, LENS, Builder, cases, max_bads, params
-from locate_model import TOO_FEW, UNKNOWN, bw_column, model_batch, powers, syndromes, xdot
+from locate_hard_cases import CAUCHY_CODES, CODES, LENS, Builder, cases, max_bads, params
+from locate_model import TOO_FEW, UNKNOWN, bw_column, model_batch, model_block, powers, syndromes, xdot
 from test_gpu_locate import model_verdicts
 from test_gpu_locate_multi import BRUTE_N, Batch
 from test_gpu_locate_multi import model_brute as multi_brute
@@ -119,7 +125,7 @@ def port_batch(gf, cs, mutate=None):
     sets = [frozenset()] * cs.B
     for b in range(cs.B):
         P = sorted(set(range(cs.n)) - cs.miss[b])
-        bd = Builder(gf, cs.k, cs.n, P, cs.T[b], None)
+        bd = Builder(gf, cs.k, cs.n, P, cs.T[b], None, cs.mult)
         u = np.array([bd.u[r] for r in P], dtype=np.uint8)
         A = mul[powers(gf, P, bd.ms), u[:, None]].T                     # row l: u_r r^l
         W = xdot(mul, A, np.ascontiguousarray(cs.bad[b][P]))
@@ -141,16 +147,40 @@ def classes(cs):
 
 @pytest.mark.parametrize("call,k,m,L,max_bad", params())
 def test_hard_batch(oracle, gf, call, k, m, L, max_bad):
-    cs = cases(oracle, gf, call, k, m, L, max_bad)
+    check_hard_batch(oracle, gf, cases(oracle, gf, call, k, m, L, max_bad), call, k, m, L, max_bad)
+
+
+@pytest.mark.parametrize("call,k,m,L,max_bad", params(cauchy=True, lens=LENS))
+def test_hard_batch_cauchy(gf, call, k, m, L, max_bad):
+    v = cauchy_oracle.code_multipliers(k, m)
+    cs = cases(cauchy_oracle, gf, call, k, m, L, max_bad, v)
+    check_hard_batch(cauchy_oracle, gf, cs, call, k, m, L, max_bad)
+    # the batch is not the kind-0 batch under another name: its blocks are no codewords without v
+    assert syndromes(gf, list(range(k + m)), cs.clean[0], k).any(axis=0).all()
+    # class e is specific to the scaled weights: without the multipliers the same bytes do not decode to
+    # the planted set, and the planted errors are no zero pivot under the weights u_r
+    specific = 0
+    for b in [b for b in range(cs.B) if cs.kind[b] == "e"]:
+        P = sorted(set(range(k + m)) - cs.miss[b])
+        (col,) = cs.cols[b].values()
+        plain = model_block(gf, k, m, P, cs.bad[b], L, max_bad)
+        W = Builder(gf, k, k + m, P, cs.T[b], None).sums(col.errs, 3)
+        zero = W[0] == 0 if len(col.errs) == 2 else gf[0][W[0], W[2]] == gf[0][W[1], W[1]]
+        specific += plain != (len(col.want), col.want) and not zero
+    assert specific >= 1 or not any(kd == "e" for kd in cs.kind)
+
+
+def check_hard_batch(oracle, gf, cs, call, k, m, L, max_bad):
+    v = cs.mult
     n, B = k + m, cs.B
     # the anchor: the oracle's blocks are polynomials of degree < k at the points 0 .. n - 1
     pts = list(range(n))
     for b in (0, B - 1):
-        assert not syndromes(gf, pts, cs.clean[b], k).any()
-        assert bw_column(gf, pts, cs.clean[b][:, L - 1], k, 0) == frozenset()
+        assert not syndromes(gf, pts, cs.clean[b], k, v).any()
+        assert bw_column(gf, pts, cs.clean[b][:, L - 1], k, 0, v) == frozenset()
     flip = cs.clean[0][:, 0].copy()
     flip[n - 1] ^= 1
-    assert bw_column(gf, pts, flip, k, 0) is None
+    assert bw_column(gf, pts, flip, k, 0, v) is None
     # by construction == by the model
     for b in range(B):
         if cs.built[b] is not None:
@@ -194,7 +224,7 @@ def test_hard_batch(oracle, gf, call, k, m, L, max_bad):
     for b in np.flatnonzero(cs.want >= 0):
         xs = sorted(cs.cols[b]) + [0]
         keep = sorted(set(pts) - cs.miss[b] - cs.sets[b])
-        assert not syndromes(gf, pts, cs.final[b][:, xs], k).any(), (b, cs.kind[b])
+        assert not syndromes(gf, pts, cs.final[b][:, xs], k, v).any(), (b, cs.kind[b])
         assert np.array_equal(cs.final[b][keep], cs.bad[b][keep]), (b, cs.kind[b])
         assert cs.kind[b] in ("a", "b") or np.array_equal(cs.final[b], cs.clean[b])
     if call == "multi" and n < 256:
@@ -206,16 +236,30 @@ def test_hard_batch(oracle, gf, call, k, m, L, max_bad):
         assert sums == sorted({m - 1, m - 2, 2}) and any(s % 2 for s in sums)
 
 
+def cauchy_cases(gf, call, k, m, L, max_bad):
+    return cases(cauchy_oracle, gf, call, k, m, L, max_bad, cauchy_oracle.code_multipliers(k, m))
+
+
 @pytest.mark.parametrize("call", ["multi", "partial"])
 @pytest.mark.parametrize("k,m", CODES)
 def test_class_a_reaches_every_number_of_corrupt_shards(oracle, gf, call, k, m):
+    check_class_a(functools.partial(cases, oracle, gf), call, k, m)
+
+
+@pytest.mark.parametrize("call", ["multi", "partial"])
+@pytest.mark.parametrize("k,m", CAUCHY_CODES)
+def test_class_a_reaches_every_number_of_corrupt_shards_cauchy(gf, call, k, m):
+    check_class_a(functools.partial(cauchy_cases, gf), call, k, m)
+
+
+def check_class_a(get, call, k, m):
     """Over the lengths of a code and radius: every t from T + 1 to min(n, m' + 2), none capped. (The 23
     blocks of a (240,16) batch, spread over three numbers of missing shards, hold 2 or 3 class a blocks
     of each: there at least 6 values of t, T + 1 among them.)"""
     for max_bad in max_bads(k, m):
         seen = {}
         for L in LENS:
-            cs = cases(oracle, gf, call, k, m, L, max_bad)
+            cs = get(call, k, m, L, max_bad)
             for b in range(cs.B):
                 if cs.kind[b] == "a":
                     seen.setdefault(len(cs.miss[b]), set()).add(cs.t[b])
@@ -233,10 +277,19 @@ def test_class_a_reaches_every_number_of_corrupt_shards(oracle, gf, call, k, m):
 @pytest.mark.parametrize("call", ["multi", "partial"])
 @pytest.mark.parametrize("k,m", CODES)
 def test_the_batches_catch_a_solver_without_its_root_checks(oracle, gf, call, k, m):
+    check_catch(gf, cases(oracle, gf, call, k, m, 33, 8), call, k, m)
+
+
+@pytest.mark.parametrize("call", ["multi", "partial"])
+@pytest.mark.parametrize("k,m", CAUCHY_CODES)
+def test_the_batches_catch_a_solver_without_its_root_checks_cauchy(gf, call, k, m):
+    check_catch(gf, cauchy_cases(gf, call, k, m, 33, 8), call, k, m)
+
+
+def check_catch(gf, cs, call, k, m):
     """The port without `count != v`, and without `ok = r < n`: each names shards in blocks of classes
     a, c or d that the model calls unknown (a code of 256 shards has no point at or above n: only the
     count of roots can go wrong there)."""
-    cs = cases(oracle, gf, call, k, m, 33, 8)
     cl = classes(cs)
     for mutate in ("count", "range"):
         pw, _ = port_batch(gf, cs, mutate)
