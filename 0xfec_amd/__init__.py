@@ -46,6 +46,8 @@ FEC_ERR_ALIGNMENT = -7
 FEC_ERR_HIP = -8
 FEC_ERR_NOMEM = -9
 FEC_ERR_NO_DEVICE = -10
+FEC_ERR_SINGULAR = -11
+FEC_ERR_NO_MATRIX = -12
 FEC_DEVICE = 0
 FEC_HOST = 1
 FEC_HOST_PINNED = 2
@@ -78,6 +80,7 @@ lib.fec_rs_prepare.argtypes = [_vp, _i, _i]
 lib.fec_rs_matrix_kind.argtypes = [_i, _i, _i, _vp]
 lib.fec_ctx_set_matrix.argtypes = [_vp, _i]
 lib.fec_ctx_get_matrix.argtypes = [_vp, ctypes.POINTER(_i)]
+lib.fec_ctx_set_custom_matrix.argtypes = [_vp, _i, _i, _vp]
 lib.fec_rs_encode_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i]
 lib.fec_rs_reconstruct_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_recover_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _i, _vp, _i]
@@ -147,6 +150,9 @@ def device_count():
 # The matrix kinds (fec_hip_matrix.h): klauspost's default, and its WithCauchyMatrix.
 FEC_MATRIX_VANDERMONDE, FEC_MATRIX_CAUCHY = 0, 1
 MATRIX_KINDS = {"vandermonde": FEC_MATRIX_VANDERMONDE, "cauchy": FEC_MATRIX_CAUCHY}
+# klauspost's WithCustomMatrix: rows registered on a Codec (Codec.set_custom_matrix). No kind of
+# MATRIX_KINDS: there is nothing for rs_matrix() to generate.
+FEC_MATRIX_CUSTOM = 2
 
 
 def _matrix_kind(matrix):
@@ -280,14 +286,28 @@ class Codec:
 
     def set_matrix(self, matrix):
         """The matrix kind (a name of MATRIX_KINDS or its number) of every RS call made from now on
-        (fec_ctx_set_matrix); legal between calls without a sync. The XOR calls ignore it."""
-        return _check(lib.fec_ctx_set_matrix(self._h, _matrix_kind(matrix)), "fec_ctx_set_matrix")
+        (fec_ctx_set_matrix); legal between calls without a sync. The XOR calls ignore it. "custom" / 2
+        switches back to the matrices registered with set_custom_matrix()."""
+        kind = FEC_MATRIX_CUSTOM if matrix == "custom" else _matrix_kind(matrix)
+        return _check(lib.fec_ctx_set_matrix(self._h, kind), "fec_ctx_set_matrix")
+
+    def set_custom_matrix(self, k, m, rows):
+        """Register `rows`, a uint8 [m, k] array of parity rows (klauspost WithCustomMatrix), as the
+        code of (k, m) and make "custom" the matrix of the RS calls made from now on
+        (fec_ctx_set_custom_matrix); legal between calls without a sync."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        if rows.shape != (m, k):
+            raise ValueError("rows must be a uint8 [m, k] array, got shape %r" % (rows.shape,))
+        return _check(lib.fec_ctx_set_custom_matrix(self._h, k, m, rows.ctypes.data), "fec_ctx_set_custom_matrix")
 
     @property
     def matrix(self):
         """The name of the ctx's matrix kind (fec_ctx_get_matrix)."""
         kind = _i(-1)
         _check(lib.fec_ctx_get_matrix(self._h, ctypes.byref(kind)), "fec_ctx_get_matrix")
+        if kind.value == FEC_MATRIX_CUSTOM:
+            return "custom"
         return next(name for name, v in MATRIX_KINDS.items() if v == kind.value)
 
     def close(self):
@@ -373,11 +393,12 @@ class Codec:
 
     def _recon(self, fn, lay, masks, status, shard_len, *mask_words):
         """fn: a C reconstruct call with its arguments before shard_len bound. Returns its return
-        code for FEC_OK and FEC_ERR_TOO_FEW_SHARDS, raises for any other."""
+        code for FEC_OK, FEC_ERR_TOO_FEW_SHARDS and (custom matrices) FEC_ERR_SINGULAR, raises for
+        any other."""
         ma, mkind = _addr(masks)
         assert (mkind == FEC_DEVICE) == (lay.kind == FEC_DEVICE), "masks must live where the shards live"
         rc = fn(*lay.args(shard_len), ma, *mask_words, _opt(status), lay.kind)
-        if rc not in (FEC_OK, FEC_ERR_TOO_FEW_SHARDS):
+        if rc not in (FEC_OK, FEC_ERR_TOO_FEW_SHARDS, FEC_ERR_SINGULAR):
             _check(rc, fn.func.__name__)
         return rc
 

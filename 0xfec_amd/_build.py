@@ -14,14 +14,14 @@ OBJ = os.path.join(HERE, "_obj")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "lib0xfec_hip.so")
 
-SOURCES = ["fec_encode.hip", "fec_encode23.hip", "fec_decode.hip", "fec_rebuild.hip", "fec_recover.hip", "fec_plan.hip", "fec_wide.hip", "fec_ragged.hip", "fec_verify.hip", "fec_locate.hip", "fec_locate_multi.hip", "fec_locate_partial.hip", "fec_update.hip", "fec_some.hip", "fec_xor.hip", "fec_synth.hip", "fec_pack.hip", "fec_probe.hip", "fec_kernels.hip", "fec_capi.cpp",
+SOURCES = ["fec_encode.hip", "fec_encode23.hip", "fec_decode.hip", "fec_rebuild.hip", "fec_recover.hip", "fec_plan.hip", "fec_plan_solve.hip", "fec_wide.hip", "fec_ragged.hip", "fec_verify.hip", "fec_locate.hip", "fec_locate_multi.hip", "fec_locate_partial.hip", "fec_update.hip", "fec_some.hip", "fec_xor.hip", "fec_synth.hip", "fec_pack.hip", "fec_probe.hip", "fec_kernels.hip", "fec_capi.cpp",
            "fec_cores.cpp", "fec_host.cpp", "fec_selftest.cpp", "fec_scheme.cpp", "fec_batch.cpp", "fec_wire.cpp", "fec_go.cpp"]
-HEADERS = ["fec_kernels.hpp", "fec_status.hpp", "fec_device.hpp", "fec_recon.hpp", "gf256.h", "rs_matrix.hpp",
+HEADERS = ["fec_kernels.hpp", "fec_status.hpp", "fec_device.hpp", "fec_recon.hpp", "fec_plan_sort.hpp", "gf256.h", "rs_matrix.hpp",
            "fec_bitslice.inc"]
 # headers of single translation units, and the host sources' fec_ctx.hpp (rebuild triggers only; not
 # part of source_hash)
-OWN_HEADERS = ["fec_flat.hpp", "fec_wide.hpp", "fec_ragged.hpp", "fec_some.hpp", "fec_verify.hpp", "fec_locate.hpp", "fec_locate_multi.hpp", "fec_locate_partial.hpp", "fec_update.hpp", "fec_ctx.hpp"]
-PUBLIC = ["fec_hip.h", "fec_hip_some_wide.h", "fec_scheme.h", "fec_batch.h", "fec_batch.hpp", "fec_scheme.hpp", "fec_wire.h", "fec_go.h", "fec_synth.h", "fec_probe.h"]
+OWN_HEADERS = ["fec_flat.hpp", "fec_wide.hpp", "fec_ragged.hpp", "fec_some.hpp", "fec_solve.hpp", "fec_verify.hpp", "fec_locate.hpp", "fec_locate_multi.hpp", "fec_locate_partial.hpp", "fec_update.hpp", "fec_ctx.hpp"]
+PUBLIC = ["fec_hip.h", "fec_hip_matrix.h", "fec_hip_some_wide.h", "fec_scheme.h", "fec_batch.h", "fec_batch.hpp", "fec_scheme.hpp", "fec_wire.h", "fec_go.h", "fec_synth.h", "fec_probe.h"]
 
 # The atomic optimizer would wrap every single-lane atomic (the sticky error words: one lane per
 # wave sets them, fec_device.hpp wave_flag) in wave-aggregation code it never needs.

@@ -63,7 +63,13 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; 
 int get_code(fec_ctx* ctx, int k, int m, Code** out) {
     if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
     if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
-    auto key = std::make_tuple(ctx->kind, k, m);
+    int reg = 0;
+    if (ctx->kind == FEC_MATRIX_CUSTOM) {
+        const auto cu = ctx->custom.find({k, m});
+        if (cu == ctx->custom.end()) return FEC_ERR_NO_MATRIX;
+        reg = cu->second;
+    }
+    auto key = std::make_tuple(ctx->kind, k, m, reg);
     auto it = ctx->codes.find(key);
     if (it != ctx->codes.end()) {
         *out = &it->second;
@@ -73,10 +79,22 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
     c.k = k;
     c.m = m;
     c.kind = ctx->kind;
-    c.matrix = rs::build_matrix_kind(c.kind, k, k + m);
+    c.solve = reg != 0;
+    if (c.solve) {   // identity on top, the registered rows below
+        const std::vector<uint8_t>& rows = ctx->custom_rows[(size_t)reg - 1].rows;
+        c.matrix.assign((size_t)(k + m) * k, 0);
+        for (int j = 0; j < k; ++j) c.matrix[(size_t)j * k + j] = 1;
+        memcpy(c.matrix.data() + (size_t)k * k, rows.data(), rows.size());
+    } else {
+        c.matrix = rs::build_matrix_kind(c.kind, k, k + m);
+    }
     if (c.matrix.empty()) return FEC_ERR_INV_SHARD_NUM;
+    // a custom code keeps the single-erasure tables (the direct and the routed decode) only if every
+    // entry of its parity rows is nonzero: only then is every single-erasure plan solvable
+    const bool single_ok =
+        !c.solve || std::find(c.matrix.begin() + (size_t)k * k, c.matrix.end(), (uint8_t)0) == c.matrix.end();
     c.logv = rs::grs_logv(c.kind, k, k + m);
-    if (c.kind != rs::kMatrixVandermonde) HIP_TRY(c.d_logv.upload(c.logv.data(), c.logv.size()));
+    if (c.kind == rs::kMatrixCauchy) HIP_TRY(c.d_logv.upload(c.logv.data(), c.logv.size()));
     if (m > 0) {
         std::vector<uint32_t> tabs((size_t)m * k * 8);
         for (int r = 0; r < m; ++r)
@@ -89,7 +107,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
         // single-erasure plans: data shard E0 lost, parity R0 the first present one; inputs are
         // the other data shards in order, then parity R0 (the first k present shards):
         // x_E0 = inv(A[R0][E0]) * (p_R0 ^ sum_{j != E0} A[R0][j] x_j)   (reed_solomon.go:124)
-        if (k + m <= FEC_MAX_DECODE_SHARDS) {
+        if (k + m <= FEC_MAX_DECODE_SHARDS && single_ok) {
             // the coefficient bytes of every single-erasure plan (small for every decodable code:
             // RS(20,30) 4 KB): the direct decode reads a wave's rows by scalar loads
             const size_t kw = ((size_t)k + 3) / 4;
@@ -105,7 +123,8 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             c.single_coef = sc;
             HIP_TRY(c.d_single_coef.upload(sc.data(), sc.size() * 4));
         }
-        if (k + m <= FEC_MAX_DECODE_SHARDS && fk::direct_table_words((uint32_t)k, (uint32_t)m) * 4 <= 16 * 1024) {
+        if (k + m <= FEC_MAX_DECODE_SHARDS && single_ok &&
+            fk::direct_table_words((uint32_t)k, (uint32_t)m) * 4 <= 16 * 1024) {
             // the same plans expanded to PermTabs (k*m*k*32 bytes; small codes only)
             std::vector<uint32_t> st(fk::direct_table_words((uint32_t)k, (uint32_t)m), 0);
             for (int e0 = 0; e0 < k; ++e0)
@@ -122,13 +141,15 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
                 }
             HIP_TRY(c.d_single.upload(st.data(), st.size() * 4));
         }
-        {   // the locate call's ratio -> column table and the field's inverses (fec_locate.hpp)
+        // (a custom code: no locate tables and no dyadic leaves; the locate calls are refused and the
+        // encode is the generic fold, whatever its rows)
+        if (!c.solve) {   // the locate call's ratio -> column table and the field's inverses (fec_locate.hpp)
             uint8_t lt[fk::kLocateTabBytes];
             if (!fk::locate_table(lt, c.matrix.data() + (size_t)k * k, (uint32_t)k, (uint32_t)m))
                 return FEC_ERR_INVALID_ARG;
             HIP_TRY(c.d_loctab.upload(lt, sizeof(lt)));
         }
-        if (fk::locate_needs_carry_tabs((uint32_t)k, (uint32_t)m)) {
+        if (!c.solve && fk::locate_needs_carry_tabs((uint32_t)k, (uint32_t)m)) {
             // locate's later passes, each row 0's tables followed by its own rows' (fec_locate.hpp)
             const size_t row = (size_t)k * 8, slab = fk::kLocateRows * row;
             const uint32_t later = fk::locate_passes((uint32_t)m) - 1;
@@ -141,7 +162,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             }
             HIP_TRY(c.d_loc_carry.upload(carry.data(), carry.size() * 4));
         }
-        if (m >= 1 && m <= fk::kLocateMultiRows) {
+        if (!c.solve && m >= 1 && m <= fk::kLocateMultiRows) {
             // the locate-multi call's coefficients as PermTabs, then the field's tables
             // (fec_locate_multi.hpp)
             uint8_t A[fk::kLocateMultiRows * fk::kLocateMultiRows];
@@ -154,7 +175,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
             memcpy(&lm[(size_t)m * m * 8], &gf::kTables, sizeof(gf::Tables));
             HIP_TRY(c.d_lmtab.upload(lm.data(), lm.size() * 4));
         }
-        const std::vector<uint8_t> leaves = dyadic_leaves(c.matrix, k, m);
+        const std::vector<uint8_t> leaves = c.solve ? std::vector<uint8_t>() : dyadic_leaves(c.matrix, k, m);
         if (!leaves.empty() && leaves.size() <= (size_t)m * k) {   // staged like m x k tables
             std::vector<uint32_t> dy((size_t)m * k * 8, 0);
             for (size_t i = 0; i < leaves.size(); ++i) {
@@ -166,7 +187,7 @@ int get_code(fec_ctx* ctx, int k, int m, Code** out) {
     }
     // (for m == 0 too: the sorted-plan kernels stage it whatever the code, and a reconstruct of a
     // code without parity, where every loss is a failed block, takes them on long shards)
-    if (k + m <= FEC_MAX_DECODE_SHARDS) {
+    if (k + m <= FEC_MAX_DECODE_SHARDS && !c.solve) {
         uint8_t dall[FEC_MAX_DECODE_SHARDS] = {};
         for (int sidx = 0; sidx < k + m; ++sidx) {
             unsigned d = 0;
@@ -252,6 +273,8 @@ const char* fec_strerror(int code) {
         case FEC_ERR_HIP: return "HIP runtime error";
         case FEC_ERR_NOMEM: return "out of memory";
         case FEC_ERR_NO_DEVICE: return "no HIP device";
+        case FEC_ERR_SINGULAR: return "matrix is singular";   // klauspost errSingular
+        case FEC_ERR_NO_MATRIX: return "no custom matrix registered for these shard counts, or a call custom matrices do not serve";
         case -21: return "EOF";   // FEC_ERR_EOF (fec_wire.h): io.EOF
         default: return "unknown error";
     }
@@ -441,8 +464,31 @@ int fec_rs_matrix_kind(int kind, int k, int m, uint8_t* out) {
 }
 
 int fec_ctx_set_matrix(fec_ctx* ctx, int kind) {
-    if (!ctx || kind < 0 || kind >= rs::kMatrixKinds) return FEC_ERR_INVALID_ARG;
+    if (!ctx || kind < 0 || (kind >= rs::kMatrixKinds && kind != FEC_MATRIX_CUSTOM)) return FEC_ERR_INVALID_ARG;
     ctx->kind = kind;
+    return FEC_OK;
+}
+
+// A registration is its rows kept on the ctx; get_code builds the code's tables on first use, keyed
+// by the registration, so a (k, m) registered again gets new tables and the old ones stay for the
+// launches that hold them.
+int fec_ctx_set_custom_matrix(fec_ctx* ctx, int k, int m, const uint8_t* parity_rows) {
+    // (the shard counts first, as the batch calls check theirs before they look at the ctx)
+    if (k <= 0 || m < 0) return FEC_ERR_INV_SHARD_NUM;
+    if (k + m > 256) return FEC_ERR_MAX_SHARD_NUM;
+    if (!ctx || !parity_rows || m == 0) return FEC_ERR_INVALID_ARG;
+    const size_t bytes = (size_t)m * k;
+    int reg = 0;
+    for (size_t i = 0; i < ctx->custom_rows.size() && !reg; ++i) {
+        const fec_ctx::CustomRows& r = ctx->custom_rows[i];
+        if (r.k == k && r.m == m && !memcmp(r.rows.data(), parity_rows, bytes)) reg = (int)i + 1;
+    }
+    if (!reg) {
+        ctx->custom_rows.push_back({k, m, std::vector<uint8_t>(parity_rows, parity_rows + bytes)});
+        reg = (int)ctx->custom_rows.size();
+    }
+    ctx->custom[{k, m}] = reg;
+    ctx->kind = FEC_MATRIX_CUSTOM;
     return FEC_OK;
 }
 
@@ -484,6 +530,7 @@ struct Call {
     int max_m = -1;            // the call's largest m (-1: none; the locate-multi call: 16)
     int max_bad = 1;           // the locate-multi call's max_bad, in [min_bad, FEC_LOCATE_MAX_BAD]
     int min_bad = 1;           // (the locate-partial call: 0)
+    bool builtin_only = false; // not served under a custom matrix (fec_hip_matrix.h): FEC_ERR_NO_MATRIX
     struct {
         const void *a, *b;
     } words[2] = {};           // (mask, status)-like pairs of 4-byte arrays, either may be null
@@ -513,6 +560,7 @@ static int check_call(fec_ctx* ctx, Call& c, Code** code) {
         return FEC_ERR_INVALID_ARG;
     int rc = select_device(ctx);
     if (rc) return rc;
+    if (c.rs && c.builtin_only && ctx->kind == FEC_MATRIX_CUSTOM) return FEC_ERR_NO_MATRIX;
     if (c.rs && (rc = get_code(ctx, c.k, c.m, code))) return rc;
     if (s.nblocks == 0 || (c.encode && c.m == 0)) return FEC_OK;
     if (!s.data || c.null_arg || (c.m > 0 && !s.parity)) return FEC_ERR_INVALID_ARG;
@@ -590,6 +638,7 @@ int fec_rs_reconstruct_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, 
     c.null_arg = !present_mask;
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_mask, block_status};
+    c.builtin_only = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
@@ -612,6 +661,7 @@ int fec_rs_recover_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
     const OutRegion o = recover_out(c, out, out_block_stride, out_slots);
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_mask, block_status};
+    c.builtin_only = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
@@ -664,6 +714,7 @@ int fec_rs_reconstruct_some_wide_batch(fec_ctx* ctx, int k, int m, size_t shard_
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_mask, block_status};
     c.words[1] = {want_mask, nullptr};
+    c.builtin_only = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
@@ -683,6 +734,7 @@ int fec_rs_locate_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size_t nbl
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_out, bad_shard};
     c.words[1] = {counts, nullptr};
+    c.builtin_only = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
@@ -701,6 +753,7 @@ int fec_rs_locate_multi_batch(fec_ctx* ctx, int k, int m, size_t shard_len, size
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_out, bad_count};
     c.words[1] = {counts, nullptr};
+    c.builtin_only = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
@@ -719,6 +772,7 @@ int fec_rs_locate_partial_batch(fec_ctx* ctx, int k, int m, size_t shard_len, si
     c.wide = true, c.mask_words = mask_words;
     c.words[0] = {present_mask, bad_count};
     c.words[1] = {present_out, counts};
+    c.builtin_only = true;
     Code* code = nullptr;
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;

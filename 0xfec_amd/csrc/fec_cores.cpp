@@ -11,6 +11,7 @@
 #include "fec_locate_multi.hpp"
 #include "fec_locate_partial.hpp"
 #include "fec_ragged.hpp"
+#include "fec_solve.hpp"
 #include "fec_some.hpp"
 #include "fec_update.hpp"
 #include "fec_verify.hpp"
@@ -93,6 +94,7 @@ int rs_encode_device(fec_ctx* ctx, Code* code, const Shards& s) {
             a.sp = fk::encode_store_policy(fk::g_tune.st_pol, {s.data, s.dbs, s.ss, (uint64_t)k},
                                            {s.parity, s.pbs, s.pss, (uint64_t)code->m}, s.len, s.nblocks);
             // (the fixed shapes are chosen by this code's own matrix: its kind, and for RS(2,3) its row)
+            // (a custom code: none, whatever its rows are)
             const fk::FixedEncode fx = fk::fixed_encode((uint32_t)k, a.m, a.dytabs != nullptr, code->kind,
                                                         code->matrix.data() + (size_t)k * k);
             if (fx != fk::FixedEncode::none) {
@@ -103,6 +105,13 @@ int rs_encode_device(fec_ctx* ctx, Code* code, const Shards& s) {
         }
         return FEC_OK;
     });
+}
+
+// The plan kernels of a code: a custom matrix takes its records from the elimination plan
+// (fec_plan_solve.hip), the same records in the same order; the rebuild kernels do not tell.
+static hipError_t launch_plan(const Code* code, const fk::PlanArgs& p, bool sorted, hipStream_t s) {
+    if (code->solve) return fk::launch_rs_plan_solve(p, sorted, s);
+    return sorted ? fk::launch_rs_plan_sorted(p, s) : fk::launch_rs_plan(p, s);
 }
 
 // What a slice's PlanArgs and ReconArgs hold in the uniform and the ragged reconstruct alike: the
@@ -161,6 +170,8 @@ int rs_reconstruct_device(fec_ctx* ctx, Code* code, const ReconCall& call) {
     //  * routed (in-place calls of RS(8,12)): a classify pass reduces the masks to one word; the
     //    sorted plans run only if some block has two or more erased data shards, and one kernel
     //    runs the direct body or the wave rebuild by that word (fec_recover.hip).
+    // A custom code has the single-erasure tables, and so the direct and the routed form, only if no
+    // entry of its parity rows is zero (get_code); its plans come from launch_plan.
     const bool single_slot = out.base && out.slots == 1;
     const bool direct = code->d_single_coef && fk::direct_recon_applies(k, m, cps, single_slot);
     const bool wave = !direct && fk::wave_recon_applies(cps, k, maxe, lay_sorted.stride);
@@ -200,14 +211,14 @@ int rs_reconstruct_device(fec_ctx* ctx, Code* code, const ReconCall& call) {
         } else if (routed) {
             a.route = p.route = ctx->work->d_wflags;
             HIP_TRY(fk::launch_rs_route_classify(a, ctx->work->d_wflags, ctx->stream));
-            HIP_TRY(fk::launch_rs_plan_sorted(p, ctx->stream));
+            HIP_TRY(launch_plan(code, p, true, ctx->stream));
             HIP_TRY(fk::launch_rs_reconstruct_routed(a, ctx->stream));
         } else if (wave) {
-            HIP_TRY(fk::launch_rs_plan_sorted(p, ctx->stream));
+            HIP_TRY(launch_plan(code, p, true, ctx->stream));
             if (fk::rebuild_k_applies(k, maxe, cps)) HIP_TRY(fk::launch_rs_rebuild_k(a, ctx->stream));
             else HIP_TRY(fk::launch_rs_reconstruct_wave(a, ctx->stream));
         } else {
-            HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
+            HIP_TRY(launch_plan(code, p, false, ctx->stream));
             HIP_TRY(fk::launch_rs_reconstruct(a, (int)std::max<uint32_t>(1, a.ntiles), ctx->stream));
         }
         return FEC_OK;
@@ -582,9 +593,10 @@ int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartial
 int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
                                const uint32_t* want) {
     const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
-    const uint8_t* logv = nullptr;
-    const int rc = code_logv(ctx, ki, mi, &logv);
+    Code* code = nullptr;   // (the entry point has looked it up already: cached)
+    const int rc = get_code(ctx, ki, mi, &code);
     if (rc) return rc;
+    const uint8_t* logv = code->d_logv;
     return rs_rebuild_tiles(ctx, k, fk::some_rows(m), s, {}, true,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
                                 const DecodeWords w = words.blocks(b0);
@@ -599,6 +611,7 @@ int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, co
                                 p.nblocks = (uint32_t)nb;
                                 p.lay = lay;
                                 p.logv = logv;
+                                if (code->solve) return fk::launch_rs_plan_solve_some({p, code->d_prows}, ctx->stream);
                                 return fk::launch_rs_plan_some(p, ctx->stream);
                             });
 }
@@ -684,7 +697,7 @@ int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, const ReconCall& call
         ra.max_len = (uint32_t)s.len;
         ra.nwin = fk::rag_windows(G, cps);
         ra.rows = rows;
-        HIP_TRY(fk::launch_rs_plan(p, ctx->stream));
+        HIP_TRY(launch_plan(code, p, false, ctx->stream));
         HIP_TRY(fk::launch_rs_reconstruct_ragged(ra, ctx->stream));
         return FEC_OK;
     });

@@ -39,6 +39,8 @@ struct DevBuf {
 struct Code {
     int k = 0, m = 0;
     int kind = 0;                  // FEC_MATRIX_* (fec_hip_matrix.h)
+    bool solve = false;            // a custom matrix: decode plans by elimination (fec_solve.hpp), no fixed-shape
+                                   // encode; d_logv, d_dall, the locate tables and d_dytabs stay null
     std::vector<uint8_t> matrix;   // n x k
     std::vector<uint8_t> logv;     // n bytes: log of shard r's multiplier v_r (rs_matrix.hpp grs_logv; zeros for kind 0)
     DevBuf<uint8_t> d_logv;        // the same on the device; null for kind 0 (the plan kernels test it)
@@ -157,7 +159,16 @@ struct fec_ctx {
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
     int kind = 0;            // the matrix kind of the RS calls made from now on (fec_hip_matrix.h)
-    std::map<std::tuple<int, int, int>, Code> codes;   // by (kind, k, m); entries stay until the ctx goes
+    // by (kind, k, m, registration: 0 for the built-in kinds); entries stay until the ctx goes
+    std::map<std::tuple<int, int, int, int>, Code> codes;
+    // fec_ctx_set_custom_matrix: every registration's parity rows (m x k; registration id = index + 1,
+    // its k and m beside it), and the registration in force for each (k, m)
+    struct CustomRows {
+        int k, m;
+        std::vector<uint8_t> rows;
+    };
+    std::vector<CustomRows> custom_rows;
+    std::map<std::pair<int, int>, int> custom;
     Work main;               // scratch of the kernels on `own` / the caller's stream
     Work* work = &main;      // scratch of the kernels on `stream` (on_stream switches both)
     int* d_err = nullptr;    // [0] sticky device-path error, [1] host-path error
@@ -183,7 +194,8 @@ inline size_t round16(size_t x) { return (x + 15) & ~size_t(15); }
 
 // ---------------------------------------------------------------- fec_capi.cpp
 int select_device(fec_ctx* ctx);
-// The ctx's code for (ctx->kind, k, m), built and cached on first use.
+// The ctx's code for (ctx->kind, k, m), built and cached on first use. Kind custom: the code of the
+// matrix registered for (k, m), FEC_ERR_NO_MATRIX when there is none.
 int get_code(fec_ctx* ctx, int k, int m, Code** out);
 // Grow the buffers that share capacity *cap (counted in units of `unit` bytes) to hold n units:
 // pinned host memory where `pinned`, else device memory. No stream may still use the old ones.

@@ -364,7 +364,7 @@ hipError_t launch_rs_encode(const EncodeArgs& a, int grid, hipStream_t s) {
 // matrix: the default and the Cauchy RS(8,12) both are, each with its own leaves), the bit-sliced
 // networks at the kind they were generated for.
 FixedEncode fixed_encode(uint32_t k, uint32_t m, bool dyadic, int kind, const uint8_t* prows) {
-    if (!g_tune.enc_fixed) return FixedEncode::none;
+    if (!g_tune.enc_fixed || kind >= 2) return FixedEncode::none;   // (a custom matrix: the generic fold)
     if (rs_encode23_applies(k, m, prows)) return FixedEncode::rs23;
     if (k == 8 && m == 4 && dyadic) return FixedEncode::dyadic84;
     if (((k == 16 && m == 8) || (k == 20 && m == 10)) && (kind == 0 || kind == 1)) return FixedEncode::bits;

@@ -372,7 +372,7 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, const Shards& s, const uint32_
     // the sticky device word of the host path: statuses report every per-block failure, but a plan
     // kernel that cannot run (fec_plan.hip form 3's LDS-alignment guard, bit 4) writes no statuses
     HIP_TRY(hipMemsetAsync(ctx->d_err + 1, 0, sizeof(int), p.comp));
-    bool failed = false;
+    bool failed = false, singular = false;   // (singular: blocks of a custom code, fec_solve.hpp)
     // A chunk's stage in a set's in buffer at `in`: the data block-major, [nb][k][ssd], then the parity
     // plane-major, [P][nb][ssd], so that only the planes a chunk reads cross PCIe.
     auto staged = [&](uint8_t* in, size_t nb) -> Shards {
@@ -458,7 +458,8 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, const Shards& s, const uint32_
         for (size_t b = 0; b < ch.nb; ++b) {
             const int32_t st = hs.h_status[b];
             if (block_status) block_status[ch.b0 + b] = st < 0 ? st : 0;
-            if (st < 0) failed = true;
+            if (st == fk::kStSingular) singular = true;
+            else if (st < 0) failed = true;
         }
         const Shards dst = s.blocks(ch.b0, ch.nb);
         parallel_for(ch.nb, [&](size_t lo, size_t hi) {
@@ -476,7 +477,7 @@ int host_reconstruct_rs(fec_ctx* ctx, Code* code, const Shards& s, const uint32_
     HIP_TRY(hipMemcpyAsync(&err, ctx->d_err + 1, sizeof(int), hipMemcpyDeviceToHost, p.comp));
     HIP_TRY(hipStreamSynchronize(p.comp));
     if ((rc = fk::sticky_rc(err & fk::kStickyInternal))) return rc;
-    return failed ? FEC_ERR_TOO_FEW_SHARDS : FEC_OK;
+    return failed ? FEC_ERR_TOO_FEW_SHARDS : singular ? FEC_ERR_SINGULAR : FEC_OK;
 }
 
 // The plain form of a FEC_HOST reconstruct, not pipelined: XOR(k,1) (the scheme mirror's per-block

@@ -14,6 +14,7 @@
 #include "fec_locate_multi.hpp"
 #include "fec_locate_partial.hpp"
 #include "fec_ragged.hpp"
+#include "fec_solve.hpp"
 #include "fec_some.hpp"
 #include "fec_wide.hpp"
 #include "gf256.h"
@@ -1234,6 +1235,186 @@ int fec__selftest_cauchy(void) {
         }
     }
     return 0;
+}
+
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- custom matrices (fec_solve.hpp)
+namespace {
+
+// The test matrices of tests/custom_model.py for (k, m), by their formulas: m x k parity rows.
+// which: 0 the default matrix's own rows, 1 cauchy255 P[i][j] = 1 / ((255 - i) ^ j), 2 par1
+// P[i][j] = (j + 1)^i, 3 lrc (8, 4): ones on columns 0-3, ones on columns 4-7, rows 0-1 of cauchy255.
+std::vector<uint8_t> custom_test_rows(int which, int k, int m) {
+    std::vector<uint8_t> P((size_t)m * k, 0);
+    if (which == 0) {
+        const std::vector<uint8_t> M = rs::build_matrix(k, k + m);
+        std::copy(M.begin() + (size_t)k * k, M.end(), P.begin());
+        return P;
+    }
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < k; ++j) {
+            const uint8_t c = gf::inv((uint8_t)((255 - i) ^ j));
+            P[(size_t)i * k + j] = which == 1 ? c : which == 2 ? gf::exp_pow((uint8_t)(j + 1), i) : 0;
+        }
+    if (which == 3)
+        for (int j = 0; j < k; ++j) {
+            P[j] = j < 4, P[(size_t)k + j] = j >= 4;
+            for (int i = 0; i < 2; ++i) P[(size_t)(2 + i) * k + j] = gf::inv((uint8_t)((255 - i) ^ j));
+        }
+    return P;
+}
+
+// What klauspost computes for one block, by another route than fec_solve.hpp: the rows of the first k
+// present shards inverted whole (rs::invert, k x k). S: those shards; T: M[o] * inverse for every
+// shard o < n (n x k). False when the rows are dependent.
+bool custom_reference(const std::vector<uint8_t>& P, uint32_t k, uint32_t n, uint32_t mask, std::vector<uint8_t>& S,
+                      std::vector<uint8_t>& T) {
+    auto M = [&](uint32_t r, uint32_t c) -> uint8_t { return r < k ? (uint8_t)(r == c) : P[(size_t)(r - k) * k + c]; };
+    S.clear();
+    for (uint32_t i = 0; i < n && S.size() < k; ++i)
+        if ((mask >> i) & 1u) S.push_back((uint8_t)i);
+    std::vector<uint8_t> inv((size_t)k * k);
+    for (uint32_t p = 0; p < k; ++p)
+        for (uint32_t c = 0; c < k; ++c) inv[(size_t)p * k + c] = M(S[p], c);
+    if (!rs::invert((int)k, inv.data())) return false;
+    T.assign((size_t)n * k, 0);
+    for (uint32_t o = 0; o < n; ++o)
+        for (uint32_t p = 0; p < k; ++p)
+            for (uint32_t t = 0; t < k; ++t) T[(size_t)o * k + p] ^= gf::mul(M(o, t), inv[(size_t)t * k + p]);
+    return true;
+}
+
+// One mask of one matrix through both record builders against custom_reference: the reconstruct /
+// recover record for 0, 1 and maxe output slots, the reconstruct-some record for the want masks
+// given. 0, or the number of the check that failed. *singular: the rows were dependent.
+int custom_check_mask(const std::vector<uint8_t>& P, uint32_t k, uint32_t m, uint32_t mask,
+                      const std::vector<uint32_t>& wants, bool* singular) {
+    const uint32_t n = k + m, all = fk::solve_low(n), kmask = fk::solve_low(k);
+    const uint32_t maxe = std::max(1u, std::min(k, m));
+    const uint8_t *ex = gf::kTables.exp, *lg = gf::kTables.log;
+    uint8_t cols[fk::kSolveColBytes], E[fk::kSolveMaxE], R[fk::kSolveMaxE];
+    const uint32_t np = fk::solve_popc(mask & all), e = k - fk::solve_popc(mask & kmask);
+    std::vector<uint8_t> S, T;
+    const bool ok = np >= k && custom_reference(P, k, n, mask, S, T);
+    *singular = np >= k && !ok;
+    for (uint32_t max_out : {0u, 1u, maxe}) {
+        const fk::PlanLayout lay = fk::plan_layout(k, maxe, max_out == 1);
+        std::vector<uint8_t> rec(lay.stride, 0xEE);
+        const fk::SolveClass got =
+            fk::solve_plan_record(rec.data(), lay, mask, k, n, max_out, P.data(), cols, E, R, ex, lg);
+        fk::BlockClass want = fk::classify_block(e, np, k, max_out);
+        if (want.nout && !ok) want = {fk::kStSingular, 0u, fk::kStickySingular};
+        if (got.status != want.status || got.nout != want.nout || got.bit != want.bit) return 1;
+        if (rec[lay.nout_off] != want.nout) return 2;
+        if (!want.nout) continue;
+        if (memcmp(&rec[lay.in_off], S.data(), k)) return 3;
+        for (uint32_t i = 0, r = 0; i < k; ++i) {
+            if ((mask >> i) & 1u) continue;
+            if (rec[lay.out_off + r] != i || memcmp(&rec[lay.coef_off + (size_t)r * k], &T[(size_t)i * k], k)) return 4;
+            ++r;
+        }
+    }
+    const fk::WideLayout lay = fk::wide_layout(k, fk::some_rows(m));
+    for (uint32_t want : wants) {
+        std::vector<uint8_t> rec(lay.stride, 0xEE);
+        const fk::SolveClass got =
+            fk::solve_some_record(rec.data(), lay, mask, want, k, n, P.data(), cols, E, R, ex, lg);
+        const uint32_t miss = ~mask & want & all, eo = fk::solve_popc(miss);
+        const int32_t st = !eo ? 0 : np < k ? fk::kStTooFew : !ok ? fk::kStSingular : 0;
+        const uint32_t nout = st ? 0u : eo;
+        if (got.status != st || got.nout != nout || rec[lay.nout_off] != nout) return 5;
+        if (got.bit != (st == fk::kStTooFew ? fk::kStickyTooFew : st ? fk::kStickySingular : 0)) return 6;
+        if (!nout) continue;
+        if (memcmp(&rec[lay.in_off], S.data(), k)) return 7;
+        for (uint32_t i = 0, r = 0; i < n; ++i) {
+            if (!((miss >> i) & 1u)) continue;
+            if (rec[lay.out_off + r] != i || memcmp(&rec[lay.coef_off + (size_t)r * k], &T[(size_t)i * k], k)) return 8;
+            ++r;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Internal self-test (not part of the public ABI, no device needed): the elimination plan of a custom
+// matrix (fec_solve.hpp: the statements the plan kernels of fec_plan_solve.hip run with a lane per
+// column) against M[O] * inverse(M[S]) by rs::invert, a full k x k inversion. The four (8, 4) test
+// matrices over every mask with 1..5 of the 12 shards missing (of those with 1..4 missing and a data
+// shard among them, 778, the default rows and cauchy255 have no singular one, par1 8, lrc 172: counted
+// here), each through the reconstruct / recover record for 0, 1 and 4 slots and the reconstruct-some
+// record for want = every shard, data shard 0, parity shard 9, what is missing, and nothing; then
+// cauchy255 of (20, 10), (16, 8), (16, 16), (1, 31), (31, 1) over 96 drawn masks each with 1..m + 1
+// missing, none singular. 0 on success, else 100000 * (matrix or shape index + 1) + 10 * case + check.
+int fec__selftest_custom_plan(void) {
+    static const int want_singular[4] = {0, 0, 8, 172};
+    for (int which = 0; which < 4; ++which) {
+        const std::vector<uint8_t> P = custom_test_rows(which, 8, 4);
+        int patterns = 0, singular = 0, ci = 0;
+        for (uint32_t mask = 0; mask < (1u << 12); ++mask) {
+            const uint32_t lost = 12 - fk::solve_popc(mask);
+            if (lost < 1 || lost > 5) continue;
+            ++ci;
+            bool sing = false;
+            const int rc = custom_check_mask(P, 8, 4, mask, {0xFFFFFFFFu, 1u, 1u << 9, ~mask, 0u}, &sing);
+            if (rc) return 100000 * (which + 1) + 10 * ci + rc;
+            if (lost <= 4 && (~mask & 0xFFu)) ++patterns, singular += sing;
+        }
+        if (patterns != 778 || singular != want_singular[which]) return 100000 * (which + 1) + 9;
+    }
+    uint64_t seed = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&seed]() -> uint32_t {
+        seed ^= seed << 13;
+        seed ^= seed >> 7;
+        seed ^= seed << 17;
+        return (uint32_t)(seed >> 16);
+    };
+    static const int shapes[][2] = {{20, 10}, {16, 8}, {16, 16}, {1, 31}, {31, 1}};
+    int si = 4;
+    for (auto& sh : shapes) {
+        ++si;
+        const uint32_t k = (uint32_t)sh[0], m = (uint32_t)sh[1], n = k + m;
+        const std::vector<uint8_t> P = custom_test_rows(1, (int)k, (int)m);
+        for (int ci = 1; ci <= 96; ++ci) {
+            uint32_t mask = fk::solve_low(n);
+            for (uint32_t lose = 1 + rnd() % (m + 1); lose > 0;) {
+                const uint32_t i = rnd() % n;
+                if ((mask >> i) & 1u) mask &= ~(1u << i), --lose;
+            }
+            bool sing = false;
+            const int rc = custom_check_mask(P, k, m, mask, {0xFFFFFFFFu, 1u << (rnd() % n), ~mask, 0u}, &sing);
+            if (rc || sing) return 100000 * si + 10 * ci + (rc ? rc : 9);
+        }
+    }
+    return 0;
+}
+
+// Internal, test-only like fec__set_tuning (not part of the public ABI, no device needed): the
+// elimination plan of one block of the code with parity rows `rows` (m x k), k + m <= 32, by the
+// statements the plan kernels run (solve_some_record). present, want: the block's masks (want
+// 0xFFFFFFFF: every shard). Returns the number of shards the plan rebuilds (the missing wanted ones,
+// ascending, into outputs_out: m bytes; their coefficient rows over the k inputs into coef_out:
+// m * k bytes; the inputs into inputs_out: k bytes), or FEC_ERR_TOO_FEW_SHARDS / FEC_ERR_SINGULAR
+// (nothing written), or FEC_ERR_INVALID_ARG.
+int fec__custom_plan(int k, int m, const uint8_t* rows, uint32_t present, uint32_t want, uint8_t* inputs_out,
+                     uint8_t* outputs_out, uint8_t* coef_out) {
+    if (k <= 0 || m <= 0 || k + m > FEC_MAX_DECODE_SHARDS || !rows || !inputs_out || !outputs_out || !coef_out)
+        return FEC_ERR_INVALID_ARG;
+    const fk::WideLayout lay = fk::wide_layout((uint32_t)k, fk::some_rows((uint32_t)m));
+    std::vector<uint8_t> rec(lay.stride, 0);
+    uint8_t cols[fk::kSolveColBytes], E[fk::kSolveMaxE], R[fk::kSolveMaxE];
+    const fk::SolveClass sc = fk::solve_some_record(rec.data(), lay, present, want, (uint32_t)k, (uint32_t)(k + m), rows,
+                                                    cols, E, R, gf::kTables.exp, gf::kTables.log);
+    if (sc.status) return sc.status;
+    if (!sc.nout) return 0;
+    memcpy(inputs_out, &rec[lay.in_off], (size_t)k);
+    memcpy(outputs_out, &rec[lay.out_off], sc.nout);
+    memcpy(coef_out, &rec[lay.coef_off], (size_t)sc.nout * k);
+    return (int)sc.nout;
 }
 
 }  // extern "C"

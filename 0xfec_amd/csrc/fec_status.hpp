@@ -21,13 +21,14 @@ namespace fk {
 constexpr int32_t kStTooFew = -4;     // fewer than k shards present and something to rebuild
 constexpr int32_t kStSlots = -1;      // recover: more erased data shards than output slots
 constexpr int32_t kStShardSize = -5;  // ragged: the block is longer than the call's max_shard_len
+constexpr int32_t kStSingular = -11;  // custom matrix: enough shards and slots, but the rows are dependent
 // The locate calls' verdicts (fec_locate.hpp, fec_locate_partial.hpp).
 constexpr int32_t kLocateClean = -1;
 constexpr int32_t kLocateUnknown = -2;
 constexpr int32_t kLocateTooFew = -3;
 
 static_assert(kStTooFew == FEC_ERR_TOO_FEW_SHARDS && kStSlots == FEC_ERR_INVALID_ARG &&
-                  kStShardSize == FEC_ERR_SHARD_SIZE,
+                  kStShardSize == FEC_ERR_SHARD_SIZE && kStSingular == FEC_ERR_SINGULAR,
               "block statuses are the public return codes");
 static_assert(kLocateClean == FEC_LOCATE_CLEAN && kLocateUnknown == FEC_LOCATE_UNKNOWN &&
                   kLocateTooFew == FEC_LOCATE_TOO_FEW,
@@ -40,15 +41,17 @@ constexpr int kStickyTooFew = 1;    // a block with too few shards
 constexpr int kStickySlots = 2;     // a recover block with more erasures than output slots
 constexpr int kStickyInternal = 4;  // internal (the form-3 plan kernel's LDS-alignment guard)
 constexpr int kStickyOversize = 8;  // a ragged call met a block longer than its max_shard_len
+constexpr int kStickySingular = 16; // a block of a custom code whose rows are dependent (fec_solve.hpp)
 
 // The return code of a sticky word (0: FEC_OK). Too few shards comes first, then the internal
-// error, then too few slots, then the oversize ragged block.
+// error, then too few slots, then the oversize ragged block, then the singular block.
 inline int sticky_rc(int err) {
     if (!err) return FEC_OK;
     return (err & kStickyTooFew)    ? FEC_ERR_TOO_FEW_SHARDS
            : (err & kStickyInternal) ? FEC_ERR_HIP
            : (err & kStickySlots)    ? FEC_ERR_INVALID_ARG
-                                     : FEC_ERR_SHARD_SIZE;
+           : (err & kStickyOversize) ? FEC_ERR_SHARD_SIZE
+                                     : FEC_ERR_SINGULAR;
 }
 
 // ------------------------------------------------------------------ classification

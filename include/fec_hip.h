@@ -120,6 +120,10 @@ extern "C" {
 #define FEC_ERR_HIP (-8)             /* HIP runtime failure */
 #define FEC_ERR_NOMEM (-9)
 #define FEC_ERR_NO_DEVICE (-10)
+#define FEC_ERR_SINGULAR (-11)       /* klauspost errSingular: the rows of the first k present shards of a
+                                        custom code matrix are dependent (fec_hip_matrix.h) */
+#define FEC_ERR_NO_MATRIX (-12)      /* kind FEC_MATRIX_CUSTOM: no matrix registered for this (k, m), or a
+                                        call that custom matrices do not serve (fec_hip_matrix.h) */
 
 #define FEC_DEVICE 0
 #define FEC_HOST 1
@@ -158,7 +162,8 @@ int fec_ctx_release_staging(fec_ctx *ctx);
  * since the last fec_sync met a block with fewer than k present shards, or
  * FEC_ERR_INVALID_ARG if a recover met a block with more erasures than output slots, or
  * FEC_ERR_SHARD_SIZE if a ragged call met a block longer than its max_shard_len and neither of
- * the other two happened (then clears it). */
+ * the other two happened, or FEC_ERR_SINGULAR if a decode under a custom matrix met a block whose
+ * rows are dependent and nothing else happened (then clears it). */
 int fec_sync(fec_ctx *ctx);
 
 /* The n x k systematic matrix of RS(k, m) (n = k + m), row-major, host memory. No device
