@@ -91,6 +91,9 @@ lib.fec_rs_encode_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp,
 lib.fec_rs_reconstruct_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
 lib.fec_rs_recover_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _i, _vp,
                                             _i]
+lib.fec_rs_verify_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _i]
+lib.fec_rs_reconstruct_some_ragged_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp,
+                                                     _i]
 lib.fec_rs_verify_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _i]
 lib.fec_rs_locate_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _i]
 lib.fec_rs_locate_multi_batch.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _i, _vp, _vp, _sz, _vp, _i]
@@ -647,6 +650,49 @@ class Codec:
 
     def rs_reconstruct_some_split(self, k, m, data, parity, masks, want=None, status=None, shard_len=None):
         return self._reconstruct_some(k, m, _Layout(k, m, data, parity, _SOME), masks, want, status, shard_len)
+
+    # ---- ragged verify and reconstruct-some (include/fec_hip_ragged.h; FEC_DEVICE only): the two calls
+    # above with lens, a uint32 / int32 device tensor [B], as the other ragged forms take it;
+    # max_shard_len defaults to the slot size S. A block longer than max_shard_len gets status
+    # FEC_ERR_SHARD_SIZE. The raw mirrors return the C return code.
+    def rs_verify_ragged_raw(self, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss, lens, status, count=None,
+                             flags=FEC_DEVICE):
+        return lib.fec_rs_verify_ragged_batch(self._h, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss, lens,
+                                              status, count, flags)
+
+    def rs_reconstruct_some_ragged_raw(self, k, m, max_shard_len, nblocks, data, dbs, parity, pbs, ss, masks, lens,
+                                       want=None, status=None, flags=FEC_DEVICE):
+        return lib.fec_rs_reconstruct_some_ragged_batch(self._h, k, m, max_shard_len, nblocks, data, dbs, parity, pbs,
+                                                        ss, masks, want, lens, status, flags)
+
+    def _verify_ragged(self, k, m, lay, lens, status, count, max_shard_len):
+        ca = None if count is None else self._words_addr(count, 1, "count")
+        return _check(self.rs_verify_ragged_raw(k, m, *lay.args(max_shard_len), self._lens_addr(lens, lay.B),
+                                                self._words_addr(status, lay.B, "status"), ca),
+                      "fec_rs_verify_ragged_batch")
+
+    def rs_verify_ragged(self, k, m, shards, lens, status, count=None, max_shard_len=None):
+        return self._verify_ragged(k, m, _Layout(k, m, shards, None, _RAGGED), lens, status, count, max_shard_len)
+
+    def rs_verify_ragged_split(self, k, m, data, parity, lens, status, count=None, max_shard_len=None):
+        return self._verify_ragged(k, m, _Layout(k, m, data, parity, _RAGGED), lens, status, count, max_shard_len)
+
+    def _reconstruct_some_ragged(self, k, m, lay, masks, lens, want, status, max_shard_len):
+        wa = None if want is None else self._words_addr(want, lay.B, "want")
+        sa = None if status is None else self._words_addr(status, lay.B, "status")
+        return _check(self.rs_reconstruct_some_ragged_raw(k, m, *lay.args(max_shard_len),
+                                                          self._words_addr(masks, lay.B, "masks"),
+                                                          self._lens_addr(lens, lay.B), wa, sa),
+                      "fec_rs_reconstruct_some_ragged_batch")
+
+    def rs_reconstruct_some_ragged(self, k, m, shards, masks, lens, want=None, status=None, max_shard_len=None):
+        return self._reconstruct_some_ragged(k, m, _Layout(k, m, shards, None, _RAGGED), masks, lens, want, status,
+                                             max_shard_len)
+
+    def rs_reconstruct_some_ragged_split(self, k, m, data, parity, masks, lens, want=None, status=None,
+                                         max_shard_len=None):
+        return self._reconstruct_some_ragged(k, m, _Layout(k, m, data, parity, _RAGGED), masks, lens, want, status,
+                                             max_shard_len)
 
     # ---- wide reconstruct-some (include/fec_hip_some_wide.h; FEC_DEVICE only; k + m <= 256): masks and want
     # (optional; None = every shard) are 4-byte integer device tensors [B, W] of one shape,

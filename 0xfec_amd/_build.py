@@ -21,7 +21,7 @@ HEADERS = ["fec_kernels.hpp", "fec_status.hpp", "fec_device.hpp", "fec_recon.hpp
 # headers of single translation units, and the host sources' fec_ctx.hpp (rebuild triggers only; not
 # part of source_hash)
 OWN_HEADERS = ["fec_flat.hpp", "fec_wide.hpp", "fec_ragged.hpp", "fec_some.hpp", "fec_solve.hpp", "fec_verify.hpp", "fec_locate.hpp", "fec_locate_multi.hpp", "fec_locate_partial.hpp", "fec_update.hpp", "fec_ctx.hpp"]
-PUBLIC = ["fec_hip.h", "fec_hip_matrix.h", "fec_hip_some_wide.h", "fec_scheme.h", "fec_batch.h", "fec_batch.hpp", "fec_scheme.hpp", "fec_wire.h", "fec_go.h", "fec_synth.h", "fec_probe.h"]
+PUBLIC = ["fec_hip.h", "fec_hip_matrix.h", "fec_hip_some_wide.h", "fec_hip_ragged.h", "fec_scheme.h", "fec_batch.h", "fec_batch.hpp", "fec_scheme.hpp", "fec_wire.h", "fec_go.h", "fec_synth.h", "fec_probe.h"]
 
 # The atomic optimizer would wrap every single-lane atomic (the sticky error words: one lane per
 # wave sets them, fec_device.hpp wave_flag) in wave-aggregation code it never needs.

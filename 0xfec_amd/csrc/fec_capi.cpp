@@ -12,6 +12,7 @@
 #include <functional>
 
 #include "../../include/fec_hip_matrix.h"
+#include "../../include/fec_hip_ragged.h"
 #include "../../include/fec_hip_some_wide.h"
 #include "fec_ctx.hpp"
 #include "fec_kernels.hpp"
@@ -858,6 +859,41 @@ int fec_rs_recover_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len
     const int rc = check_call(ctx, c, &code);
     if (rc != kRun) return rc;
     return rs_reconstruct_ragged_device(ctx, code, {c.s, {present_mask, 1, block_status, ctx->d_err}, o}, block_len);
+}
+
+// Ragged verify and reconstruct-some (fec_hip_ragged.h): their uniform calls' checks, block_len among
+// the pointers.
+int fec_rs_verify_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks, const uint8_t* data,
+                               size_t data_block_stride, const uint8_t* parity, size_t parity_block_stride,
+                               size_t shard_stride, const uint32_t* block_len, int32_t* block_status,
+                               uint32_t* mismatch_count, int flags) {
+    Call c{k, m, 256, false, flags,
+           shards(max_shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
+    c.null_arg = !block_status || !block_len;
+    c.words[0] = {mismatch_count, block_status};
+    c.words[1] = {block_len, nullptr};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_verify_ragged_device(ctx, code, c.s, block_len, block_status, mismatch_count, ctx->d_err);
+}
+
+// (m == 0: the parity region is neither read nor written)
+int fec_rs_reconstruct_some_ragged_batch(fec_ctx* ctx, int k, int m, size_t max_shard_len, size_t nblocks,
+                                         uint8_t* data, size_t data_block_stride, uint8_t* parity,
+                                         size_t parity_block_stride, size_t shard_stride,
+                                         const uint32_t* present_mask, const uint32_t* want_mask,
+                                         const uint32_t* block_len, int32_t* block_status, int flags) {
+    Call c{k, m, FEC_MAX_DECODE_SHARDS, false, flags,
+           shards(max_shard_len, nblocks, data, data_block_stride, parity, parity_block_stride, shard_stride)};
+    c.null_arg = !present_mask || !block_len;
+    c.words[0] = {present_mask, block_status};
+    c.words[1] = {want_mask, block_len};
+    Code* code = nullptr;
+    const int rc = check_call(ctx, c, &code);
+    if (rc != kRun) return rc;
+    return rs_reconstruct_some_ragged_device(ctx, k, m, c.s, {present_mask, 1, block_status, ctx->d_err}, want_mask,
+                                             block_len);
 }
 
 int fec_xor_encode_batch(fec_ctx* ctx, int k, size_t shard_len, size_t nblocks, const uint8_t* data,

@@ -588,31 +588,38 @@ int rs_locate_partial_device(fec_ctx* ctx, const Code* code, const LocatePartial
                                 [&](uint8_t* ws, auto run) { return locate_partial_launches(code, pc, ws, run); });
 }
 
+// Reconstruct-some's plan kernel for one launch slice of nb blocks from block b0: records of layout
+// `lay` in block order into the stream's workspace, from the present and want masks (want null: every
+// shard); a custom code's come from the elimination plan (fec_plan_solve.hip). They do not depend on
+// the shard length: the uniform and the ragged call take the same.
+static hipError_t plan_some_slice(fec_ctx* ctx, const Code* code, const DecodeWords& words, const uint32_t* want,
+                                  size_t b0, size_t nb, const fk::WideLayout& lay) {
+    const DecodeWords w = words.blocks(b0);
+    fk::SomePlanArgs p{};
+    p.masks = w.masks;
+    p.want = want ? want + b0 : nullptr;
+    p.plans = ctx->work->d_plans;
+    p.status = w.status;
+    p.err = w.err;
+    p.k = (uint32_t)code->k;
+    p.n = (uint32_t)(code->k + code->m);
+    p.nblocks = (uint32_t)nb;
+    p.lay = lay;
+    p.logv = code->d_logv;
+    if (code->solve) return fk::launch_rs_plan_solve_some({p, code->d_prows}, ctx->stream);
+    return fk::launch_rs_plan_some(p, ctx->stream);
+}
+
 // Reconstruct-some (fec_some.hip): plan records in block order from the present and want masks, then
 // the wide tile, storing into both regions.
 int rs_reconstruct_some_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
                                const uint32_t* want) {
-    const uint32_t k = (uint32_t)ki, m = (uint32_t)mi;
     Code* code = nullptr;   // (the entry point has looked it up already: cached)
     const int rc = get_code(ctx, ki, mi, &code);
     if (rc) return rc;
-    const uint8_t* logv = code->d_logv;
-    return rs_rebuild_tiles(ctx, k, fk::some_rows(m), s, {}, true,
+    return rs_rebuild_tiles(ctx, (uint32_t)ki, fk::some_rows((uint32_t)mi), s, {}, true,
                             [&](size_t b0, size_t nb, const fk::WideLayout& lay) {
-                                const DecodeWords w = words.blocks(b0);
-                                fk::SomePlanArgs p{};
-                                p.masks = w.masks;
-                                p.want = want ? want + b0 : nullptr;
-                                p.plans = ctx->work->d_plans;
-                                p.status = w.status;
-                                p.err = w.err;
-                                p.k = k;
-                                p.n = k + m;
-                                p.nblocks = (uint32_t)nb;
-                                p.lay = lay;
-                                p.logv = logv;
-                                if (code->solve) return fk::launch_rs_plan_solve_some({p, code->d_prows}, ctx->stream);
-                                return fk::launch_rs_plan_some(p, ctx->stream);
+                                return plan_some_slice(ctx, code, words, want, b0, nb, lay);
                             });
 }
 
@@ -699,6 +706,80 @@ int rs_reconstruct_ragged_device(fec_ctx* ctx, Code* code, const ReconCall& call
         ra.rows = rows;
         HIP_TRY(launch_plan(code, p, false, ctx->stream));
         HIP_TRY(fk::launch_rs_reconstruct_ragged(ra, ctx->stream));
+        return FEC_OK;
+    });
+}
+
+// Ragged verify: rs_verify_device's presets (statuses 1, the count 0, on the stream), then the ragged
+// encode's launches with the stored parity folded in; the first row pass gives oversize blocks their
+// status, after the memset in stream order.
+int rs_verify_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,
+                            uint32_t* count, int* err) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)status, 1, s.nblocks, ctx->stream));
+    if (count) HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+    const uint32_t cps = chunks_of(s.len);
+    const uint32_t G = ragged_encode_blocks(cps);
+    return for_flat_slices(s, [&](const Shards& sl, size_t b0) -> int {
+        for (int r0 = 0; r0 < code->m; r0 += 16) {
+            fk::RagVerifyArgs a{};
+            fill_row_pass(a, code, r0, sl);
+            a.par = sl.par(0, r0);
+            a.par_bs = sl.pbs;
+            a.max_len = (uint32_t)sl.len;
+            a.nblocks = (uint32_t)sl.nblocks;
+            a.g = G;
+            a.nwin = fk::rag_windows(G, cps);
+            a.lens = lens + b0;
+            a.status = status + b0;
+            a.count = count;
+            a.err = err;
+            a.report = r0 == 0;
+            HIP_TRY(fk::launch_rs_verify_ragged(a, ctx->stream));
+        }
+        return FEC_OK;
+    });
+}
+
+// Ragged reconstruct-some: the uniform call's records (plan_some_slice), then the ragged tile over
+// them, which also overrides the status of oversize blocks. Blocks per tile as the ragged rebuild's,
+// within what LDS holds of one row pass of tables and the record per block.
+int rs_reconstruct_some_ragged_device(fec_ctx* ctx, int ki, int mi, const Shards& s, const DecodeWords& words,
+                                      const uint32_t* want, const uint32_t* lens) {
+    if (s.ss >> 32) return FEC_ERR_INVALID_ARG;   // the rebuild takes 32-bit shard strides
+    Code* code = nullptr;   // (the entry point has looked it up already: cached)
+    const int rc0 = get_code(ctx, ki, mi, &code);
+    if (rc0) return rc0;
+    const uint32_t k = (uint32_t)ki, rows = fk::some_rows((uint32_t)mi);
+    const uint32_t cps = chunks_of(s.len);
+    const fk::WideLayout lay = fk::wide_layout(k, rows);
+    const size_t per_launch = blocks_per_launch(s.nblocks, cps, lay.stride);
+    const int rc = grow_plans(ctx, per_launch * lay.stride);
+    if (rc) return rc;
+    const int forced = fk::g_tune.rag_g;
+    uint32_t G = forced > 0 ? (uint32_t)forced : std::max<uint32_t>(1, fk::kRagWindow / cps);
+    G = fk::rag_clamp_blocks(std::min(G, fk::rag_some_max_blocks(k, rows, lay)), cps);
+    return for_slices(s.nblocks, per_launch, [&](size_t b0, size_t nb) -> int {
+        const Shards sl = s.blocks(b0, nb);
+        const DecodeWords w = words.blocks(b0);
+        fk::RagSomeArgs a{};
+        a.data = sl.data;
+        a.parity = sl.parity;
+        a.dbs = sl.dbs;
+        a.pbs = sl.pbs;
+        a.ss = (uint32_t)sl.ss;
+        a.plans = ctx->work->d_plans;
+        a.lay = lay;
+        a.k = k;
+        a.nblocks = (uint32_t)nb;
+        a.max_len = (uint32_t)s.len;
+        a.g = G;
+        a.nwin = fk::rag_windows(G, cps);
+        a.rows = rows;
+        a.lens = lens + b0;
+        a.status = w.status;
+        a.err = w.err;
+        HIP_TRY(plan_some_slice(ctx, code, words, want, b0, nb, lay));
+        HIP_TRY(fk::launch_rs_reconstruct_some_ragged(a, ctx->stream));
         return FEC_OK;
     });
 }

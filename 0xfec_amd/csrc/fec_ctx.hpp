@@ -268,6 +268,11 @@ int rs_reconstruct_some_wide_device(fec_ctx* ctx, int k, int m, const Shards& s,
                                     const uint32_t* want);
 int rs_encode_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,
                             int* err);
+// The ragged forms of verify and reconstruct-some (s.len: max_shard_len; lens: nblocks lengths).
+int rs_verify_ragged_device(fec_ctx* ctx, Code* code, const Shards& s, const uint32_t* lens, int32_t* status,
+                            uint32_t* count, int* err);
+int rs_reconstruct_some_ragged_device(fec_ctx* ctx, int k, int m, const Shards& s, const DecodeWords& w,
+                                      const uint32_t* want, const uint32_t* lens);
 int xor_encode_device(fec_ctx* ctx, int k, const Shards& s);
 int xor_reconstruct_device(fec_ctx* ctx, int k, const Shards& s, const DecodeWords& w);
 

@@ -1,5 +1,6 @@
 // fec_ragged.hpp — ragged batches (a shard length per block): the item arithmetic shared by the
-// kernels of fec_ragged.hip and the host self-test (fec__selftest_ragged_tiles, fec_selftest.cpp), and
+// kernels of fec_ragged.hip and the host self-tests (fec__selftest_ragged_tiles and
+// fec__selftest_ragged_some, fec_selftest.cpp), and
 // the launch interface of fec_ragged.hip.
 //
 // A workgroup takes one window of one tile. A tile is G consecutive blocks; its items are the
@@ -15,6 +16,7 @@
 #include <stdint.h>
 
 #include "fec_kernels.hpp"
+#include "fec_wide.hpp"
 #include "gf256.h"
 
 namespace fk {
@@ -109,11 +111,65 @@ struct RagReconArgs {
     uint32_t rows;             // rows a block can need: min(r.maxe, a recover's out slots)
 };
 
-// Blocks per tile the rebuild may hold in LDS beside its prefix arrays (64 KiB budget), with `rows`
-// table rows per block.
+// Ragged verify: one pass of m <= 16 parity rows over the encode's tiles and windows, the stored
+// parity folded in (fec_verify.hpp VerifyArgs).
+struct RagVerifyArgs {
+    const uint8_t* in;         // data shard 0 of block 0
+    const uint8_t* par;        // the pass's first parity shard of block 0
+    uint64_t in_bs, par_bs, ss;
+    uint32_t k, m;             // m: parity rows of this pass (<= 16)
+    uint32_t max_len, nblocks;
+    uint32_t g, nwin;
+    const uint32_t* lens;
+    int32_t* status;           // nblocks words, 1 on entry (or 0 from an earlier pass)
+    uint32_t* count;           // optional: blocks whose status went from 1 to 0
+    int* err;                  // sticky error word (an oversize block)
+    uint32_t report;           // the first row pass: oversize blocks get their status
+    const uint32_t* tabs;      // m * k PermTabs of this pass, device memory
+};
+
+// Ragged reconstruct-some: the records of fec_some.hpp (WideLayout, `rows` = some_rows(m) rows, block
+// order), rebuilt shards into their own slots of the data and the parity region. Output rows go in
+// passes of kWideRowPass; a block's tables of one pass take rag_some_pass_rows(rows) * k entries.
+struct RagSomeArgs {
+    uint8_t* data;
+    uint8_t* parity;
+    uint64_t dbs, pbs;
+    uint32_t ss;
+    const uint8_t* plans;
+    WideLayout lay;
+    uint32_t k, nblocks, max_len;
+    uint32_t g, nwin;
+    uint32_t rows;             // rows a record holds
+    const uint32_t* lens;
+    int32_t* status;           // optional; the plan kernel's, overridden for oversize blocks
+    int* err;
+};
+
+// Table rows a block keeps in LDS at a time, and the row passes of a record of `rows` rows.
+GF_HD inline uint32_t rag_some_pass_rows(uint32_t rows) { return rows < kWideRowPass ? rows : kWideRowPass; }
+GF_HD inline uint32_t rag_some_passes(uint32_t rows) { return (rows + kWideRowPass - 1) / kWideRowPass; }
+// The rows the kernel instance that serves passes of prow rows is compiled for (12: RS(20,30)'s ten
+// rows, as the ragged rebuild's 12-row instance).
+GF_HD inline uint32_t rag_some_instance(uint32_t prow) {
+    return prow <= 1 ? 1u : prow <= 2 ? 2u : prow <= 4 ? 4u : prow <= 8 ? 8u : prow <= 12 ? 12u : kWideRowPass;
+}
+// The rows block-local pass p (from row p * kWideRowPass) rebuilds of a block with nout outputs.
+GF_HD inline uint32_t rag_some_rows_in_pass(uint32_t nout, uint32_t r0) {
+    return nout > r0 ? (nout - r0 < kWideRowPass ? nout - r0 : kWideRowPass) : 0u;
+}
+
+// Blocks per tile the rebuilds may hold in LDS beside their prefix arrays (64 KiB budget, so that more
+// than one workgroup fits a CU): the reconstruct with `rows` table rows per block, reconstruct-some
+// with one row pass of tables and the whole record per block; and the LDS a tile of g blocks takes.
 uint32_t rag_recon_max_blocks(uint32_t k, uint32_t rows, const PlanLayout& lay);
+uint32_t rag_some_max_blocks(uint32_t k, uint32_t rows, const WideLayout& lay);
+size_t rag_some_lds(uint32_t g, uint32_t k, uint32_t rows, const WideLayout& lay);
+constexpr size_t kRagLdsBudget = 64u * 1024u;
 
 hipError_t launch_rs_encode_ragged(const RagEncodeArgs& a, hipStream_t s);
 hipError_t launch_rs_reconstruct_ragged(const RagReconArgs& a, hipStream_t s);
+hipError_t launch_rs_verify_ragged(const RagVerifyArgs& a, hipStream_t s);
+hipError_t launch_rs_reconstruct_some_ragged(const RagSomeArgs& a, hipStream_t s);
 
 }  // namespace fk

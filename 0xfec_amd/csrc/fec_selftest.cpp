@@ -990,6 +990,56 @@ int fec__selftest_ragged_tiles(void) {
     return 0;
 }
 
+// Internal self-test (not part of the public ABI, no device needed): the host-side arithmetic of the
+// ragged reconstruct-some (fec_ragged.hpp rag_some_*), over every code k + m <= 32 (m = 0 included)
+// and cps_max in {1, 76, 4375, 2^26}: the blocks per tile the launch is given (a full window's worth,
+// and every forced rag_g of the tests, clamped as the core clamps them) are at least 1, at most one
+// lane per block, keep a tile's local items within 32 bits and its LDS within the 64 KiB budget, and
+// the largest tile is the largest that fits; a record's rows fall into rag_some_passes(rows) passes
+// of at most kWideRowPass rows, each row of each possible output count in exactly one pass, and the
+// rows a block keeps tables for cover every pass; the kernel instance compiled for a pass holds its
+// rows. 0 on success, else 1000 * k + 10 * m + the failing check.
+int fec__selftest_ragged_some(void) {
+    static const uint32_t cpss[] = {1, 76, 4375, 1u << 26};
+    static const uint32_t forced[] = {0, 1, 3, 16, 256, 100000};
+    for (uint32_t k = 1; k <= 32; ++k)
+        for (uint32_t m = 0; k + m <= 32; ++m) {
+            const int fail = (int)(1000 * k + 10 * m);
+            const uint32_t rows = fk::some_rows(m);
+            const fk::WideLayout lay = fk::wide_layout(k, rows);
+            const uint32_t gmax = fk::rag_some_max_blocks(k, rows, lay);
+            if (gmax < 1 || gmax > fk::kRagMaxTileBlocks) return fail + 1;
+            if (fk::rag_some_lds(gmax, k, rows, lay) > fk::kRagLdsBudget) return fail + 2;
+            if (gmax < fk::kRagMaxTileBlocks && fk::rag_some_lds(gmax + 1, k, rows, lay) <= fk::kRagLdsBudget)
+                return fail + 3;
+            // the tables and the records of a tile lie behind one another, 16-byte aligned
+            if (lay.stride % 16 || fk::rag_some_lds(1, k, rows, lay) % 16) return fail + 4;
+            for (uint32_t cps : cpss)
+                for (uint32_t f : forced) {
+                    uint32_t G = f ? f : std::max<uint32_t>(1, fk::kRagWindow / cps);
+                    G = fk::rag_clamp_blocks(std::min(G, gmax), cps);
+                    if (G < 1 || G > gmax || (uint64_t)G * cps > fk::kRagMaxTileItems) return fail + 5;
+                    if ((uint64_t)fk::rag_windows(G, cps) * fk::kRagWindow < (uint64_t)G * cps) return fail + 6;
+                }
+            const uint32_t passes = fk::rag_some_passes(rows), prow = fk::rag_some_pass_rows(rows);
+            if (prow < 1 || prow > fk::kWideRowPass || passes * fk::kWideRowPass < rows ||
+                (passes - 1) * fk::kWideRowPass >= rows)
+                return fail + 7;
+            for (uint32_t nout = 0; nout <= rows; ++nout) {
+                uint32_t seen = 0;
+                for (uint32_t p = 0; p < passes; ++p) {
+                    const uint32_t my = fk::rag_some_rows_in_pass(nout, p * fk::kWideRowPass);
+                    if (my > prow) return fail + 8;
+                    seen += my;
+                }
+                if (seen != nout || fk::rag_some_rows_in_pass(nout, passes * fk::kWideRowPass)) return fail + 8;
+            }
+            const uint32_t maxe = fk::rag_some_instance(prow);
+            if (maxe < prow || maxe > fk::kWideRowPass) return fail + 9;
+        }
+    return 0;
+}
+
 // Internal self-test (not part of the public ABI, no device needed): the wide plan's coefficient
 // rows (fec_wide.hpp wide_logsum / wide_coef, the functions rs_plan_wide_kernel runs) equal the
 // rows of the inverse of the first-k-present submatrix of the systematic matrix, for 64 seeded

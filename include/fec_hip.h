@@ -23,6 +23,9 @@
  *                               Encode / ReconstructData / the copy-out for a batch whose blocks
  *                               each have their own shard length, as the reference's blocks do
  *                               (2 + biggestSourceSymbolLenSoFar, reed_solomon.go:47,80)
+ *   fec_rs_verify_ragged_batch, fec_rs_reconstruct_some_ragged_batch (fec_hip_ragged.h)
+ *                               Verify and Reconstruct / ReconstructSome for such a batch: with them the
+ *                               whole Encoder surface takes a shard length per block
  *   fec_rs_verify_batch         Encoder.Verify(shards), batched: one verdict per block (klauspost's
  *                               interface; the reference does not call it)
  *   fec_rs_locate_batch         no counterpart: which shard of a block that fails Verify is the corrupt
@@ -62,7 +65,7 @@
  * and a block's or shard's offset from its base may be any value that the alignment rules admit,
  * beyond 2^32 included; the regions of one call need not lie in one allocation. One limit: the
  * calls that rebuild shards (fec_rs_reconstruct_batch, fec_rs_recover_batch, their wide and ragged
- * forms, fec_rs_reconstruct_some_batch) take shard strides below 2^32 and return
+ * forms, fec_rs_reconstruct_some_batch and its forms) take shard strides below 2^32 and return
  * FEC_ERR_INVALID_ARG for a shard_stride of 2^32 or more, before anything is enqueued. Every other
  * call takes any shard stride.
  *
@@ -91,7 +94,8 @@
  * The wide decode calls take FEC_MASK_WORDS(k + m)..8 mask words per block and decode every code
  * the library encodes, k + m <= FEC_MAX_WIDE_SHARDS = 256. A wide call with k + m <= 32 and one
  * mask word is forwarded to the narrow call. The ragged calls follow the uniform ones: encode
- * k + m <= 256, reconstruct and recover k + m <= 32.
+ * k + m <= 256, reconstruct and recover k + m <= 32; of those in fec_hip_ragged.h,
+ * fec_rs_verify_ragged_batch k + m <= 256 and fec_rs_reconstruct_some_ragged_batch k + m <= 32.
  *
  * Threading: a ctx has one HIP stream and is used by one caller at a time (the
  * reference's manager is per connection and not thread-safe either: manager.go:41-48).

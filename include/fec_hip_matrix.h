@@ -53,9 +53,11 @@ int fec_ctx_get_matrix(fec_ctx *ctx, int *kind);
  * device.
  *
  * Under kind FEC_MATRIX_CUSTOM an RS call for a (k, m) with no registered matrix returns
- * FEC_ERR_NO_MATRIX before any device work. Served: encode, ragged encode, update, encode-idx and
- * verify for every k + m <= 256, and for k + m <= FEC_MAX_DECODE_SHARDS reconstruct, recover, their
- * ragged forms and reconstruct-some, with the host-resident forms of all of these. The wide
+ * FEC_ERR_NO_MATRIX before any device work. Served: encode, ragged encode, update, encode-idx,
+ * verify and ragged verify (fec_rs_verify_ragged_batch, fec_hip_ragged.h) for every k + m <= 256, and
+ * for k + m <= FEC_MAX_DECODE_SHARDS reconstruct, recover, their ragged forms, reconstruct-some and
+ * ragged reconstruct-some (fec_rs_reconstruct_some_ragged_batch), with the host-resident forms of the
+ * calls that have one. The wide
  * reconstruct and recover calls, wide reconstruct-some (each with more than one mask word or a code
  * of more than FEC_MAX_DECODE_SHARDS shards) and the three locate calls are not served under a custom
  * matrix: they return FEC_ERR_NO_MATRIX before any device work.
